@@ -1,13 +1,23 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native CICE4 hot path (contract: see DESIGN.md section "Measurement").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gx1|tenth|gx3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gx1|tenth|gx3] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the EVP hot loop over the whole grid = ndte subcycles of
 stress + stepu + halo update (source/ice_dyn_evp.F90:347-404 of the reference) on
-device-resident state.  `value` = EVP subcycles per second for the whole job.  The same
-JSON line carries the column-thermodynamics rate ((cell,category) updates per second),
-the HBM roofline of the dominant kernel and a CPU baseline timed on this host.
+device-resident state.  `value` = EVP subcycles per second for the whole job, from exactly K timed
+steps; `ms_per_step` = the milliseconds one of them took.  A plain run sets up, warms up, times the K
+steps and prints the line.  --full adds what the headline does not need: repeated blocks of K steps
+(spread) and blocks with HIP events around every launch (roofline), the column-thermodynamics rate
+((cell,category) updates per second), the PCIe-inclusive drop-in calls, the 0.1-degree sub-record, a
+CPU baseline timed on this host and, at N > 1 on gx1, the cross-rank one-launch loop tried in a second
+set of rank processes.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed -- u, v, the 12 stresses and
+the fields the last subcycle writes, as the caller of the path downloads them -- goes to DIR/<name>.npy
+(float64; at N > 1 DIR/rank<r>_<name>.npy).  The timed steps start from the seeded synthetic state
+(uploaded again after the clock ramp), so the same arguments give the same inputs on every run.  Above
+60 MiB in all, every field is cut to the same seeded sample of its cells (flattened).
 
 N > 1: one rank per GPU; the grid is cut into N j-slabs (strong scaling) and ghost rows travel by RCCL
 point-to-point inside the library.  Either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE /
@@ -70,6 +80,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: spread over repeated blocks, roofline, thermodynamics, "
+                        "PCIe-inclusive calls, the 0.1-degree sub-record, CPU baseline, the cross-rank-loop attempt at N > 1")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step computed to DIR/<name>.npy (float64, under 64 MB in all)")
     p.add_argument("--workload", default="gx1",
                    help="gx3, gx1, tenth, or NXxNY[xNDTE] (diagnostic: a synthetic grid of that size, e.g. the "
                         "320x72 slab one of 8 ranks works on at gx1)")
@@ -258,7 +273,7 @@ def try_peer_loop(args, rank, world, dist):
     for k in [k for k in env if k.startswith("TORCHELASTIC_")]:
         del env[k]      # (under torchrun the parents use the agent's store; the children bring their own on their own port)
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--peer-loop", "--peer-verify", "--no-peer-try",
-           "--steps", str(args.steps), "--warmup", str(args.warmup), "--ramp-seconds", str(args.ramp_seconds), "--no-tenth",
+           "--steps", str(args.steps), "--warmup", str(args.warmup), "--ramp-seconds", str(args.ramp_seconds), "--full", "--no-tenth",
            "--no-thermo", "--no-cpu-baseline", "--no-dropin-timing", "--comm-timeout", str(min(args.comm_timeout, 60.0))]
     progress("gx1: trying the cross-rank one-launch loop in a second set of rank processes")
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE if rank == 0 else subprocess.DEVNULL, start_new_session=True)
@@ -775,8 +790,9 @@ def run_cpu_baseline(args):
 
 
 def measure_evp(ctx, args, wl, rank, world, dist, torch, have_torch_gpu, steps, warmup, ramp_seconds, tune=True,
-                min_timed_s=1.0, max_repeats=400):
-    """W warm-up + exactly K timed steps of the EVP hot loop on resident state for workload `wl`.
+                min_timed_s=1.0, max_repeats=400, full=True, dump=False):
+    """W warm-up + exactly K timed steps of the EVP hot loop on resident state for workload `wl`; `full`: then the further
+    blocks of K steps (spread, per-launch events) and the roofline; `dump`: what the last timed step computed (`outputs`).
     Returns everything the JSON line needs (rank-local cell counts already reduced over the ranks)."""
     progress(f"{wl}: building the synthetic case")
     peer_loop = bool(getattr(args, "peer_loop", False)) and world > 1
@@ -919,9 +935,6 @@ def measure_evp(ctx, args, wl, rank, world, dist, torch, have_torch_gpu, steps, 
     for _ in range(n_ramp[0]):
         ctx.evp_subcycles(1, ndte)
     sync_all()
-    for _ in range(warmup):
-        ctx.evp_subcycles(1, ndte)
-    sync_all()
     # N > 1, sweeps between refreshes: the sweep in front of a refresh can run as edge + interior launches with the refresh
     # beside the interior (Evp::launch_subcycle_skew_split).  Whether that pays depends on what the exchange costs on THIS
     # machine -- timed here, both forms, a few steps each, the maximum over the ranks decides for all of them.
@@ -944,14 +957,22 @@ def measure_evp(ctx, args, wl, rank, world, dist, torch, have_torch_gpu, steps, 
         refresh_overlap = {"what": "the sweep in front of a refresh as edge + interior launches, the refresh beside the interior",
                            "ms_per_step_one_launch": 1e3 * tms[0], "ms_per_step_split": 1e3 * tms[1], "used": bool(use)}
         progress(f"{wl}: refresh overlap {'ON' if use else 'off'} ({refresh_overlap})")
+    # The ramp ran as many steps as its time asked for: the warm-up and timed steps start from the seeded state again, so that
+    # what the last timed step computes depends on the arguments alone (--dump-outputs).  Same scalars: the graph stays.
+    ctx.evp_upload(state)
+    with bounded(args.comm_timeout if world > 1 else 0, "ghost exchange of the restored state (evp_prepare)"):
+        ctx.evp_prepare(DT)
+        ctx.sync()
+    for _ in range(warmup):
+        ctx.evp_subcycles(1, ndte)
+    sync_all()
     progress(f"{wl}: ramp ({n_ramp[0]} steps) and warm-up done, timing {steps} steps")
-    # EXACTLY `steps` steps between barrier + synchronise on both sides, maximum over the ranks -- and that block
-    # repeated until about `min_timed_s` of device time have been timed (a 13 ms block alone is not a measurement):
-    # the reported block is the MEDIAN one; minimum, maximum and the number of blocks go into the line.
-    # Two kinds of blocks, alternating: the ones `value` comes from run the steps as a caller does; the others carry the HIP-event
-    # bracket of every launch (`us_per_launch` of the roofline) -- two event records per launch cost a step of the one-launch
-    # loop 7 us of its 585 (scripts/step_overhead.py; 20 us before the events lived with the object), which is the
-    # instrument's time, not the path's.  Both medians are in the line (timing.ms_per_step_with_event_bracket).
+    # EXACTLY `steps` steps between barrier + synchronise on both sides, maximum over the ranks: `value` and `ms_per_step`.
+    # --full: that block repeated until about `min_timed_s` of device time have been timed (median, minimum, maximum and the
+    # number of blocks go into `timing`).  Two kinds of further blocks, alternating: the ones like the first run the steps as
+    # a caller does; the others carry the HIP-event bracket of every launch (`us_per_launch` of the roofline) -- two event
+    # records per launch cost a step of the one-launch loop 7 us of its 585 (scripts/step_overhead.py; 20 us before the
+    # events lived with the object), which is the instrument's time, not the path's (timing.ms_per_step_with_event_bracket).
     def one_block(events=False):
         sync_all()
         t0 = time.perf_counter()
@@ -966,27 +987,34 @@ def measure_evp(ctx, args, wl, rank, world, dist, torch, have_torch_gpu, steps, 
             t, dev = float(tt[0]), float(tt[1])
         return t, dev
     measured_before = ctx.evp_get_info("skew_balanced") if skew_k else 0     # sweeps the library has measured (and synchronised on) so far
-    blocks, eblocks = [one_block()], [one_block(True)]
-    n_rep = [int(min(max_repeats, max(1, np.ceil(min_timed_s / max(blocks[0][0], 1e-6))))) - 1]
-    if dist is not None:
-        dist.broadcast_object_list(n_rep, src=0)
-    for _ in range(n_rep[0]):
-        blocks.append(one_block())
-        eblocks.append(one_block(True))
-    order = sorted(range(len(blocks)), key=lambda k: blocks[k][0])
-    t_evp = blocks[order[len(order) // 2]][0]
-    eorder = sorted(range(len(eblocks)), key=lambda k: eblocks[k][0])
-    t_events, dev_ms = eblocks[eorder[len(eorder) // 2]]
-    measured_inside = (ctx.evp_get_info("skew_balanced") - measured_before) if skew_k else 0
-    timing = {"blocks": len(blocks), "steps_per_block": steps, "timed_region_s": sum(b[0] for b in blocks),
-              # sweeps whose workgroup times the library read back INSIDE the timed blocks (eager launch + synchronisation each:
-              # the re-cut of the segment table, one loop in 96; 0 = every timed sweep replayed the graph)
-              "sweeps_measured_inside_timed_region": measured_inside,
-              "ms_per_step_median": 1e3 * t_evp / steps, "ms_per_step_min": 1e3 * blocks[order[0]][0] / steps,
-              "ms_per_step_max": 1e3 * blocks[order[-1]][0] / steps,
-              "event_blocks": len(eblocks), "ms_per_step_with_event_bracket": 1e3 * t_events / steps,
-              "note": "value: the median of `blocks` blocks of exactly `steps` steps without per-launch events; roofline.us_per_launch: HIP "
-                      "events around every launch in `event_blocks` further blocks of the same steps, alternating with the first kind"}
+    blocks = [one_block()]
+    t_evp = blocks[0][0]
+    outputs = evp_outputs(ctx, state) if dump else None
+    timing = {"blocks": 1, "steps_per_block": steps, "timed_region_s": t_evp,
+              "note": "value and ms_per_step: one block of exactly `steps` steps between device synchronisations, no per-launch events"}
+    if full:
+        eblocks = [one_block(True)]
+        n_rep = [int(min(max_repeats, max(1, np.ceil(min_timed_s / max(blocks[0][0], 1e-6))))) - 1]
+        if dist is not None:
+            dist.broadcast_object_list(n_rep, src=0)
+        for _ in range(n_rep[0]):
+            blocks.append(one_block())
+            eblocks.append(one_block(True))
+        order = sorted(range(len(blocks)), key=lambda k: blocks[k][0])
+        t_med = blocks[order[len(order) // 2]][0]
+        eorder = sorted(range(len(eblocks)), key=lambda k: eblocks[k][0])
+        t_events, dev_ms = eblocks[eorder[len(eorder) // 2]]
+        measured_inside = (ctx.evp_get_info("skew_balanced") - measured_before) if skew_k else 0
+        timing.update({"blocks": len(blocks), "timed_region_s": sum(b[0] for b in blocks),
+                       # sweeps whose workgroup times the library read back INSIDE the timed blocks (eager launch + synchronisation
+                       # each: the re-cut of the segment table, one loop in 96; 0 = every timed sweep replayed the graph)
+                       "sweeps_measured_inside_timed_region": measured_inside,
+                       "ms_per_step_median": 1e3 * t_med / steps, "ms_per_step_min": 1e3 * blocks[order[0]][0] / steps,
+                       "ms_per_step_max": 1e3 * blocks[order[-1]][0] / steps,
+                       "event_blocks": len(eblocks), "ms_per_step_with_event_bracket": 1e3 * t_events / steps,
+                       "note": "value and ms_per_step: the first of `blocks` blocks of exactly `steps` steps without per-launch events "
+                               "(the rest give median / min / max); roofline.us_per_launch: HIP events around every launch in "
+                               "`event_blocks` further blocks of the same steps, alternating with the first kind"})
     if dist is not None:
         cells = torch.tensor([nt, nu], dtype=torch.int64)
         dist.all_reduce(cells, op=dist.ReduceOp.SUM)
@@ -1008,97 +1036,99 @@ def measure_evp(ctx, args, wl, rank, world, dist, torch, have_torch_gpu, steps, 
                 ("three workgroups per CU (chosen after the first step: the ice cover leaves most tiles empty)" if dense
                  else "one workgroup per CU (the dense shape timed out on this box)"))
     n_step, main_sub = launches_per_step(ndte, fused, dom.get("overlap", 0), 0 if resident else skew_k)
-    n_launch = steps if resident else n_step * steps
-    us_per_launch = dev_ms * 1e3 / n_launch
-    sub_per_launch = nsub_total / n_launch
-    cells_rank = nt_all / world
-    # Compulsory HBM bytes of ONE LAUNCH as the kernel is built: the 12 stresses and u, v are read and written
-    # once and the 20 read-only inputs are read once per launch, however many subcycles the launch runs
-    # (k_subcycle: 1, k_subcycle2: 2) = 384 B per active T-cell per launch.  SURVEY section 8(d) counts the same
-    # 384 B per cell per SUBCYCLE; for a two-subcycle launch that figure is twice what has to cross HBM (it gave
-    # "fractions" > 1 in round 1), so it is reported separately as `survey_8d` and is NOT a roofline fraction.
-    bytes_per_launch = EVP_BYTES_PER_CELL * cells_rank
-    achieved = bytes_per_launch / (us_per_launch * 1e-6) / 1e9
-    granules = resident and bool(ctx.evp_get_info("resident_granules"))
-    kname = ("k_evp_resident (all ndte subcycles in one launch: stresses, metrics, forcing resident in registers / LDS; "
-             + ("free-running loop without a workgroup barrier, tile-edge velocities as data-tagged granules: one 16-byte sc1 store, "
-                "polled by the lanes that need them)" if granules else
-                "tile-edge velocities through agent-scope stores, progress words and agent-scope loads)") if resident else
-             f"k_subcycle_skew ({skew_k} subcycles per sweep: a pipeline of {skew_k} time levels, rows handed on through LDS; "
-             f"stress + stepu + on-rank halo per level)" if skew_k else
-             "k_subcycle2 (two subcycles per launch: stress + stepu + stress + stepu + on-rank halo)" if fused
-             else "k_subcycle (fused stress + stepu + on-rank halo)")
-    ksub = (f"k_evp_resident<{rw}, false, false, false, {'true' if granules else 'false'}>" if resident else
-            f"k_subcycle_skew<{skew_k}, false, false" if skew_k else
-            f"k_subcycle2<{fw}, false, false, {'true' if derive else 'false'}>" if fused
-            else f"k_subcycle<{waves}, {rows}, false, false, {'true' if derive else 'false'}>")
-    traffic, traffic_src = pmc_traffic(wl, ksub) if world == 1 else (None, None)
-    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "basis": "compulsory bytes of one launch: 384 B per active T-cell per launch (sigma, u, v read+written, "
-                         "20 inputs read, once per launch whatever the number of subcycles in it)",
-                "kernel": kname, "us_per_launch": us_per_launch, "bytes_per_launch": bytes_per_launch,
-                "bytes_per_unit": EVP_BYTES_PER_CELL, "unit_of_work": "active T-cell x launch",
-                "units_per_launch": cells_rank, "subcycles_per_launch": sub_per_launch,
-                "compulsory_bytes_fused": bytes_per_launch,
-                "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
-                "frac_measured_traffic": (traffic / (us_per_launch * 1e-6) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                "survey_8d": {"bytes_per_unit": EVP_BYTES_PER_CELL, "unit_of_work": "active T-cell x subcycle",
-                              "units_per_launch": cells_rank * sub_per_launch,
-                              "algorithmic_GBps": achieved * sub_per_launch,
-                              "ratio_to_peak": achieved * sub_per_launch / HBM_PEAK_GBS,
-                              "note": "north_star's per-subcycle figure (what an unfused subcycle would have to move per "
-                                      "second at this rate); exceeds what this kernel moves by the factor subcycles_per_launch"}}
-    if resident:
-        # The resident loop reads and writes the state once per ndte subcycles: HBM is no longer what bounds it, and the
-        # fraction above says only that.  What does: fp64 issue on the busiest SIMD (3 of the 12 wavefronts of a
-        # workgroup) and the cross-XCD hand-off of the tile-edge velocities once per subcycle.
-        sq = pmc_counters(wl, ksub)
-        us_sub = us_per_launch / sub_per_launch
-        roofline["not_hbm_bound"] = {
-            "us_per_subcycle": us_sub,
-            "binding": "fp64 VALU issue of the busiest SIMD + one cross-XCD hand-off (write-through store -> load through memory: 1.3-1.4 us "
-                       "store to arrival, measured) per subcycle; the VALU count includes the poll's instructions",
-            "valu_inst_per_wave_per_subcycle": sq.get("valu_per_wave_subcycle") if sq else None,
-            "issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz": (3 * sq["valu_per_wave_subcycle"] * 4 / 2400.0) if sq else None,
-            "counters_source": sq.get("source") if sq else None}
-        if sq:   # the fraction that means something for this kernel: fp64 issue slots of the busiest SIMD that are used
-            roofline["bound_effective"] = "valu_f64_issue"
-            nh = roofline["not_hbm_bound"]
-            counted = nh["issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz"] / us_sub
-            if granules:
-                # The free-running loop WAITS by polling: its counted VALU instructions include the polls' (address arithmetic,
-                # tag compares), which are not work.  The arithmetic of a subcycle is the same code as in the barrier loop,
-                # whose waits issue next to nothing: 575 VALU instructions per wavefront (profiles/r04_sq_counters.csv,
-                # profiles/r02_sq_counters_resident.csv).  `frac_valu_issue` is the fraction by THAT count.
-                nh["valu_inst_per_wave_per_subcycle_arithmetic"] = ARITH_VALU_PER_WAVE_SUBCYCLE
-                nh["arithmetic_issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz"] = 3 * ARITH_VALU_PER_WAVE_SUBCYCLE * 4 / 2400.0
-                roofline["frac_valu_issue_counting_the_polls"] = counted
-                roofline["frac_valu_issue"] = nh["arithmetic_issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz"] / us_sub
-            else:
-                roofline["frac_valu_issue"] = counted
-            ghz, src = inkernel_clock(wl)
-            if ghz:   # the same fraction at the clock the kernel really holds (2.4 GHz is the nominal figure)
-                roofline["clock_ghz"] = ghz
-                roofline["clock_source"] = src
-                roofline["frac_valu_issue_at_measured_clock"] = roofline["frac_valu_issue"] * 2.4 / ghz
-    if skew_k and not resident:
-        # The sweep moves the state once per K subcycles and is bound by fp64 issue, not by HBM: both fractions side by side.
-        # VALU instructions per launch from the archived SQ pass (every one takes 4 cycles on a 16-lane SIMD; 1,024 SIMDs
-        # at 2.4 GHz), divided by the launch time measured in THIS run.
-        sq = pmc_counters(wl, ksub) if world == 1 else None
-        if sq and sq.get("valu_insts_per_launch"):
-            issue_us = sq["valu_insts_per_launch"] * 4.0 / 1024.0 / 2400.0
-            roofline["frac_valu_issue"] = issue_us / us_per_launch
-            roofline["valu"] = {"insts_per_launch": sq["valu_insts_per_launch"], "issue_us_per_launch_at_2p4GHz": issue_us,
-                                "counters_source": sq["source"], "counters_commit": sq.get("commit")}
-            if roofline["frac_valu_issue"] > roofline["frac"]:
+    roofline = None
+    if full:     # per-launch time from the event blocks, bytes and archived counters of the kernel
+        n_launch = steps if resident else n_step * steps
+        us_per_launch = dev_ms * 1e3 / n_launch
+        sub_per_launch = nsub_total / n_launch
+        cells_rank = nt_all / world
+        # Compulsory HBM bytes of ONE LAUNCH as the kernel is built: the 12 stresses and u, v are read and written
+        # once and the 20 read-only inputs are read once per launch, however many subcycles the launch runs
+        # (k_subcycle: 1, k_subcycle2: 2) = 384 B per active T-cell per launch.  SURVEY section 8(d) counts the same
+        # 384 B per cell per SUBCYCLE; for a two-subcycle launch that figure is twice what has to cross HBM (it gave
+        # "fractions" > 1 in round 1), so it is reported separately as `survey_8d` and is NOT a roofline fraction.
+        bytes_per_launch = EVP_BYTES_PER_CELL * cells_rank
+        achieved = bytes_per_launch / (us_per_launch * 1e-6) / 1e9
+        granules = resident and bool(ctx.evp_get_info("resident_granules"))
+        kname = ("k_evp_resident (all ndte subcycles in one launch: stresses, metrics, forcing resident in registers / LDS; "
+                 + ("free-running loop without a workgroup barrier, tile-edge velocities as data-tagged granules: one 16-byte sc1 store, "
+                    "polled by the lanes that need them)" if granules else
+                    "tile-edge velocities through agent-scope stores, progress words and agent-scope loads)") if resident else
+                 f"k_subcycle_skew ({skew_k} subcycles per sweep: a pipeline of {skew_k} time levels, rows handed on through LDS; "
+                 f"stress + stepu + on-rank halo per level)" if skew_k else
+                 "k_subcycle2 (two subcycles per launch: stress + stepu + stress + stepu + on-rank halo)" if fused
+                 else "k_subcycle (fused stress + stepu + on-rank halo)")
+        ksub = (f"k_evp_resident<{rw}, false, false, false, {'true' if granules else 'false'}>" if resident else
+                f"k_subcycle_skew<{skew_k}, false, false" if skew_k else
+                f"k_subcycle2<{fw}, false, false, {'true' if derive else 'false'}>" if fused
+                else f"k_subcycle<{waves}, {rows}, false, false, {'true' if derive else 'false'}>")
+        traffic, traffic_src = pmc_traffic(wl, ksub) if world == 1 else (None, None)
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "basis": "compulsory bytes of one launch: 384 B per active T-cell per launch (sigma, u, v read+written, "
+                             "20 inputs read, once per launch whatever the number of subcycles in it)",
+                    "kernel": kname, "us_per_launch": us_per_launch, "bytes_per_launch": bytes_per_launch,
+                    "bytes_per_unit": EVP_BYTES_PER_CELL, "unit_of_work": "active T-cell x launch",
+                    "units_per_launch": cells_rank, "subcycles_per_launch": sub_per_launch,
+                    "compulsory_bytes_fused": bytes_per_launch,
+                    "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
+                    "frac_measured_traffic": (traffic / (us_per_launch * 1e-6) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                    "survey_8d": {"bytes_per_unit": EVP_BYTES_PER_CELL, "unit_of_work": "active T-cell x subcycle",
+                                  "units_per_launch": cells_rank * sub_per_launch,
+                                  "algorithmic_GBps": achieved * sub_per_launch,
+                                  "ratio_to_peak": achieved * sub_per_launch / HBM_PEAK_GBS,
+                                  "note": "north_star's per-subcycle figure (what an unfused subcycle would have to move per "
+                                          "second at this rate); exceeds what this kernel moves by the factor subcycles_per_launch"}}
+        if resident:
+            # The resident loop reads and writes the state once per ndte subcycles: HBM is no longer what bounds it, and the
+            # fraction above says only that.  What does: fp64 issue on the busiest SIMD (3 of the 12 wavefronts of a
+            # workgroup) and the cross-XCD hand-off of the tile-edge velocities once per subcycle.
+            sq = pmc_counters(wl, ksub)
+            us_sub = us_per_launch / sub_per_launch
+            roofline["not_hbm_bound"] = {
+                "us_per_subcycle": us_sub,
+                "binding": "fp64 VALU issue of the busiest SIMD + one cross-XCD hand-off (write-through store -> load through memory: 1.3-1.4 us "
+                           "store to arrival, measured) per subcycle; the VALU count includes the poll's instructions",
+                "valu_inst_per_wave_per_subcycle": sq.get("valu_per_wave_subcycle") if sq else None,
+                "issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz": (3 * sq["valu_per_wave_subcycle"] * 4 / 2400.0) if sq else None,
+                "counters_source": sq.get("source") if sq else None}
+            if sq:   # the fraction that means something for this kernel: fp64 issue slots of the busiest SIMD that are used
                 roofline["bound_effective"] = "valu_f64_issue"
-            ghz, src = inkernel_clock(wl)
-            if ghz:   # the sweep holds about 2.1 GHz, not the nominal 2.4: its issue fraction at the clock it runs at
-                roofline["clock_ghz"] = ghz
-                roofline["clock_source"] = src
-                roofline["frac_valu_issue_at_measured_clock"] = roofline["frac_valu_issue"] * 2.4 / ghz
+                nh = roofline["not_hbm_bound"]
+                counted = nh["issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz"] / us_sub
+                if granules:
+                    # The free-running loop WAITS by polling: its counted VALU instructions include the polls' (address arithmetic,
+                    # tag compares), which are not work.  The arithmetic of a subcycle is the same code as in the barrier loop,
+                    # whose waits issue next to nothing: 575 VALU instructions per wavefront (profiles/r04_sq_counters.csv,
+                    # profiles/r02_sq_counters_resident.csv).  `frac_valu_issue` is the fraction by THAT count.
+                    nh["valu_inst_per_wave_per_subcycle_arithmetic"] = ARITH_VALU_PER_WAVE_SUBCYCLE
+                    nh["arithmetic_issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz"] = 3 * ARITH_VALU_PER_WAVE_SUBCYCLE * 4 / 2400.0
+                    roofline["frac_valu_issue_counting_the_polls"] = counted
+                    roofline["frac_valu_issue"] = nh["arithmetic_issue_us_per_subcycle_3_waves_per_simd_at_2p4GHz"] / us_sub
+                else:
+                    roofline["frac_valu_issue"] = counted
+                ghz, src = inkernel_clock(wl)
+                if ghz:   # the same fraction at the clock the kernel really holds (2.4 GHz is the nominal figure)
+                    roofline["clock_ghz"] = ghz
+                    roofline["clock_source"] = src
+                    roofline["frac_valu_issue_at_measured_clock"] = roofline["frac_valu_issue"] * 2.4 / ghz
+        if skew_k and not resident:
+            # The sweep moves the state once per K subcycles and is bound by fp64 issue, not by HBM: both fractions side by side.
+            # VALU instructions per launch from the archived SQ pass (every one takes 4 cycles on a 16-lane SIMD; 1,024 SIMDs
+            # at 2.4 GHz), divided by the launch time measured in THIS run.
+            sq = pmc_counters(wl, ksub) if world == 1 else None
+            if sq and sq.get("valu_insts_per_launch"):
+                issue_us = sq["valu_insts_per_launch"] * 4.0 / 1024.0 / 2400.0
+                roofline["frac_valu_issue"] = issue_us / us_per_launch
+                roofline["valu"] = {"insts_per_launch": sq["valu_insts_per_launch"], "issue_us_per_launch_at_2p4GHz": issue_us,
+                                    "counters_source": sq["source"], "counters_commit": sq.get("commit")}
+                if roofline["frac_valu_issue"] > roofline["frac"]:
+                    roofline["bound_effective"] = "valu_f64_issue"
+                ghz, src = inkernel_clock(wl)
+                if ghz:   # the sweep holds about 2.1 GHz, not the nominal 2.4: its issue fraction at the clock it runs at
+                    roofline["clock_ghz"] = ghz
+                    roofline["clock_source"] = src
+                    roofline["frac_valu_issue_at_measured_clock"] = roofline["frac_valu_issue"] * 2.4 / ghz
     config = {"workload": workload(wl)[3] if COVER == "full" else workload(wl)[3].replace("full ice cover", f"ice cover '{COVER}' (diagnostic)"),
               "nx_global": dom["nxg"], "ny_global": dom["nyg"], "ndte": ndte,
               "subcycles_per_step": ndte,
@@ -1126,7 +1156,40 @@ def measure_evp(ctx, args, wl, rank, world, dist, torch, have_torch_gpu, steps, 
                                         "one-launch loop from the same state: u, v and the 12 stresses bit-identical on every "
                                         "rank, no fall-back before or during the timed steps")
     return dict(dom=dom, grid=grid, state=state, ndte=ndte, value=value, t_evp=t_evp, config=config,
-                roofline=roofline, steps=steps, warmup=warmup, timing=timing)
+                roofline=roofline, steps=steps, warmup=warmup, timing=timing, outputs=outputs)
+
+
+# what a caller of the timed path gets back after a step: u, v, the 12 stresses, and what the subcycle with ksub == ndte
+# writes (ice_dyn_evp.F90:347-404: deformations, ridging rates, internal and ocean stress)
+DUMP_FIELDS = ("uvel", "vvel") + synth.SIG_NAMES + ("divu", "shear", "rdg_conv", "rdg_shear", "prs_sig",
+                                                    "strintx", "strinty", "strocnx", "strocny")
+DUMP_BYTES = 60 << 20      # --dump-outputs: the data of all files of all ranks together (headroom under 64 MB)
+DUMP_SEED = 20261003
+
+
+def evp_outputs(ctx, state):
+    """DUMP_FIELDS of the device state, downloaded (cice_evp_download) into fresh host arrays"""
+    shape = state["uvel"].shape
+    s = {k: np.zeros(shape) for k in DUMP_FIELDS}
+    s["iceumask"] = np.zeros(shape, np.int32)
+    ctx.evp_download(s)
+    return {k: s[k] for k in DUMP_FIELDS}
+
+
+def write_outputs(path, outputs, rank, world):
+    """outputs -> path/<name>.npy as float64; above this rank's share of DUMP_BYTES every field is cut to the same seeded
+    sample of its (flattened) cells"""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // world
+    size = next(iter(outputs.values())).size
+    idx = None
+    if 8 * size * len(outputs) > budget:
+        n = budget // (8 * len(outputs))
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, size, n))
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for k, a in outputs.items():
+        a = np.asarray(a, np.float64)
+        np.save(os.path.join(path, prefix + k + ".npy"), a if idx is None else a.reshape(-1)[idx])
 
 
 def measure_thermo(ctx, args, wl, dom, world, dist, torch, steps):
@@ -1217,12 +1280,14 @@ def main():
         calib = {"kernel": "k_diag_copy8", "bytes_read": nd * 8, "bytes_written": nd * 8, "ms": ms,
                  "GBps": 2 * nd * 8 / (ms * 1e-3) / 1e9}
     m = measure_evp(ctx, args, args.workload, rank, world, dist, torch, have_torch_gpu, args.steps, args.warmup,
-                    args.ramp_seconds)
+                    args.ramp_seconds, full=args.full, dump=bool(args.dump_outputs))
     dom, state, ndte = m["dom"], m["state"], m["ndte"]
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, m.pop("outputs"), rank, world)
 
     # ---- N > 1, gx1: the cross-rank one-launch loop, tried and verified in a second set of processes (see try_peer_loop)
     peer_try = None
-    if (world > 1 and args.workload == "gx1" and not args.peer_loop and not args.no_peer_try
+    if (args.full and world > 1 and args.workload == "gx1" and not args.peer_loop and not args.no_peer_try
             and os.environ.get("CICE4_AMD_BENCH_PEER_CHILD") is None):
         try:
             peer_try = try_peer_loop(args, rank, world, dist)
@@ -1234,7 +1299,7 @@ def main():
 
     # ---- the drop-in form evp(dt) with host arrays on both sides (PCIe-inclusive; never `value`)
     pcie = None
-    if world == 1 and not args.no_dropin_timing:
+    if args.full and world == 1 and not args.no_dropin_timing:
         st2 = {k: v.copy() for k, v in state.items()}
         ctx.evp_pin_fields(st2)       # what the Fortran drop-in does with its module arrays on the first call
 
@@ -1268,7 +1333,7 @@ def main():
         del st2
 
     # ---- thermo (secondary figure)
-    thermo, tcols = (None, None) if args.no_thermo else measure_thermo(ctx, args, args.workload, dom, world, dist, torch, args.steps)
+    thermo, tcols = (None, None) if args.no_thermo or not args.full else measure_thermo(ctx, args, args.workload, dom, world, dist, torch, args.steps)
 
     # ---- PCIe-inclusive thermodynamic half-step: cice_step_therm1 (one upload, frzmlt + thermo x ncat + merge_fluxes
     # on the device, one download), host arrays page-locked once.  Never `value`.
@@ -1361,7 +1426,7 @@ def main():
 
     # ---- the 0.1-degree configuration (BASELINE.json configs[4]) inside the same line: a short run, EVP only + thermo
     tenth = None
-    if args.workload == "gx1" and not args.no_tenth:
+    if args.full and args.workload == "gx1" and not args.no_tenth:
         del state
         m["state"] = m["grid"] = None
         t = measure_evp(ctx, args, "tenth", rank, world, dist, torch, have_torch_gpu, args.tenth_steps, 1, 0.3, tune=False,
@@ -1396,15 +1461,17 @@ def main():
             # `steps` x `ms_per_step` describes ONE block of exactly K steps (the median block); the timed region as a whole
             # is that block repeated `timing.blocks` times, each between barrier + synchronise: this many seconds
             "timed_region_s": m["timing"]["timed_region_s"], "timed_blocks": m["timing"]["blocks"],
-            "timing": m["timing"], "config": m["config"], "roofline": m["roofline"],
+            "timing": m["timing"], "config": m["config"],
         }
+        if m["roofline"] is not None:
+            out["roofline"] = m["roofline"]
         if peer_try:
             # two decompositions were measured; `value` is the faster one, the other stays in the line
             slabs = {"value": out["value"], "ms_per_step": out["ms_per_step"], "timing": out["timing"], "config": out["config"]}
             if peer_try.get("value") and peer_try["value"] > out["value"]:
                 peer_try["used"] = True
                 out.update(value=peer_try["value"], ms_per_step=peer_try["ms_per_step"], timing=peer_try["timing"],
-                           config=peer_try["config"], roofline=peer_try["roofline"] or out["roofline"])
+                           config=peer_try["config"], roofline=peer_try["roofline"] or out.get("roofline"))
                 out["other_decomposition"] = dict(slabs, what="wide-halo slabs, RCCL exchange every `overlap` subcycles")
             else:
                 if peer_try.get("value"):
@@ -1420,11 +1487,12 @@ def main():
         if pcie:
             out["pcie_inclusive"] = pcie
         # the archived counter passes this line quotes (traffic, VALU counts, in-kernel clock): do they describe THIS tree's kernels?
-        out["counters_stale"] = bool(STALE)
-        out["counters"] = {"kernel_source_sha": kernel_source_sha(), "stale_sources": list(STALE),
-                           "note": "traffic, frac_valu_issue and clock_ghz come from archived rocprofv3 passes under profiles/ "
-                                   "(not measured in this run); stale: taken from kernel sources other than this tree's"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["counters_stale"] = bool(STALE)
+            out["counters"] = {"kernel_source_sha": kernel_source_sha(), "stale_sources": list(STALE),
+                               "note": "traffic, frac_valu_issue and clock_ghz come from archived rocprofv3 passes under profiles/ "
+                                       "(not measured in this run); stale: taken from kernel sources other than this tree's"}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             progress("cpu baseline (child process)")
             cb = run_cpu_baseline(args)
             out["cpu_baseline"] = dict(cb.get("evp") or {"value": None, "unit": "EVP subcycles/s", "cores": 0,

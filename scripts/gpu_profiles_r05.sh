@@ -14,11 +14,11 @@ cp commit.txt $O/commit.txt 2>/dev/null || echo unknown > $O/commit.txt
 python -c "import bench; print(bench.kernel_source_sha())" > $O/source_sha.txt
 B="--no-cpu-baseline --no-dropin-timing"
 if [ $PART = all ] || [ $PART = stats ]; then
-  timeout -k 10 500 python bench.py > $O/bench_gx1.json 2> $O/bench_gx1.err || echo "bench failed"
+  timeout -k 10 500 python bench.py --full > $O/bench_gx1.json 2> $O/bench_gx1.err || echo "bench failed"
   echo bench-done
   rm -rf $O/stats_gx1 $O/stats_tenth_full $O/stats_tenth_caps
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_gx1 -- python bench.py --steps 5 --warmup 1 --no-tenth --no-thermo $B > $O/stats_gx1.log 2>&1 || echo "stats gx1 failed"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_gx1_thermo -- python bench.py --steps 5 --warmup 1 --no-tenth $B > $O/stats_gx1_thermo.log 2>&1 || echo "stats gx1 thermo failed"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_gx1_thermo -- python bench.py --full --steps 5 --warmup 1 --no-tenth $B > $O/stats_gx1_thermo.log 2>&1 || echo "stats gx1 thermo failed"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_tenth_full -- python bench.py --workload tenth --steps 3 --warmup 1 --no-thermo $B > $O/stats_tenth_full.log 2>&1 || echo "stats tenth full failed"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_tenth_caps -- python bench.py --workload tenth --cover caps --steps 3 --warmup 1 --no-thermo $B > $O/stats_tenth_caps.log 2>&1 || echo "stats tenth caps failed"
   echo stats-done
@@ -28,7 +28,7 @@ for wl in gx1 tenth; do
   if [ $PART = all ] || [ $PART = pmc ]; then
     for c in FETCH_SIZE WRITE_SIZE; do
       rm -rf $O/pmc_${c}_$wl
-      timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${c}_$wl -- python bench.py $X --steps 1 --warmup 0 --ramp-seconds 0 $B --calibrate > $O/pmc_${c}_$wl.log 2>&1 || echo "pmc $c $wl failed"
+      timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${c}_$wl -- python bench.py --full $X --steps 1 --warmup 0 --ramp-seconds 0 $B --calibrate > $O/pmc_${c}_$wl.log 2>&1 || echo "pmc $c $wl failed"
     done
     echo pmc-$wl-done
   fi

@@ -10,8 +10,10 @@ if ROOT not in sys.path:
 
 # Several tests run the ranks of a multi-rank job as contexts of this process whose one-launch loops wait for each other: each
 # needs a hardware queue of its own (on a node each has a GPU of its own).  The runtime multiplexes its streams on four
-# queues unless told otherwise -- read when it starts, hence here, before anything touches the device.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# queues unless told otherwise -- read when it starts, hence here, before anything touches the device.  An environment
+# that already asks for fewer (four is the runtime's default, and some hosts set it explicitly) is raised to eight.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 8:
+    os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 
 def pytest_configure(config):

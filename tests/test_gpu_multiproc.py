@@ -127,7 +127,8 @@ def test_bench_tries_and_verifies_the_cross_rank_loop_by_itself():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-tenth", "--no-cpu-baseline", "--no-thermo"], capture_output=True, text=True, timeout=800, env=env)
+                        "--full", "--no-tenth", "--no-cpu-baseline", "--no-thermo"], capture_output=True, text=True, timeout=800,
+                       env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
