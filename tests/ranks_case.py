@@ -24,13 +24,18 @@ def owned(dom, f):
 
 
 def run_ranks(gg, R, mode, ndte, dt, ns=0, seed=31, cover="patchy", overlap=0, skew_k=0, split=None, strength_args=None,
-              min_cells=None, timeout=600, info=None, npx=1, blocks=(1, 1), block_map=None):
+              min_cells=None, timeout=600, info=None, npx=1, blocks=(1, 1), block_map=None, by_side=False, setup=None, check=None):
     """Run evp(dt) on R ranks (threads) and return [(dom, state)] per rank.
     mode: 'classic' (one block per rank, ghost cells after every subcycle), 'peer' (the whole loop in one launch per rank,
     neighbours' exchange copies mapped), 'slabs' (wide-halo slabs with `overlap` rows; skew_k > 0: K-subcycle sweeps
     between the refreshes).  npx: task columns of the cartesian layout (classic / peer; R / npx task rows): 1 = j-slabs;
     blocks = (bx, by): every task holds bx x by blocks of its part of the grid.  block_map = (bsx, bsy, owner): any block -> rank
     map instead (owner[g] = rank of global block g, -1: an eliminated land block; cice_domain_create_map).
+    ns: 0 closed, 1 cyclic north-south (the caller's grid has no land rows then), 3 / 4 a tripole fold on the top rank.
+    by_side: 'peer' on j-slabs connects through the older call (cice_evp_peer_connect: 0 = the rank to the south, 1 = to the
+    north -- the only one that can name the same rank twice, ns = 1 on two ranks) instead of cice_evp_peer_connect_rank.
+    setup(c, r, R): the caller's own options and assertions on rank r, after evp_init and the mode's options, before the
+    peer buffers are exported; check(c, r, R): its assertions after the step, before any rank frees its buffers.
     info: optional dict that receives what rank 0 reports (evp_get_info)."""
     nxg, nyg = gg["nxg"], gg["nyg"]
     _LINK[0] += 1
@@ -46,7 +51,7 @@ def run_ranks(gg, R, mode, ndte, dt, ns=0, seed=31, cover="patchy", overlap=0, s
             # another rank creates in between would shift the count)
             bar.wait(timeout=120)
             if mode == "slabs":
-                dom = c.domain_create_slabs(nxg, nyg, R, ew=1, ns=0, rank=r, nranks=R, overlap=overlap)
+                dom = c.domain_create_slabs(nxg, nyg, R, ew=1, ns=ns, rank=r, nranks=R, overlap=overlap)
             elif block_map is not None:
                 bsx, bsy, owner = block_map
                 dom = c.domain_create_map(nxg, nyg, bsx, bsy, owner, ew=1, ns=ns, rank=r, nranks=R)
@@ -62,21 +67,6 @@ def run_ranks(gg, R, mode, ndte, dt, ns=0, seed=31, cover="patchy", overlap=0, s
             c.evp_init(grid, ndte=ndte, **kw)
             if mode == "peer":
                 c.evp_set_option("resident_peer_share", R)
-                exports[r] = c.evp_peer_export()
-                bar.wait(timeout=120)
-                if npx == 1 and R <= 3 and blocks == (1, 1) and block_map is None:   # the older call: by side (0 = the rank to the south, 1 = to the north)
-                    if r > 0 or ns == 1:
-                        c.evp_peer_connect(0, exports[(r - 1) % R])
-                    if r < R - 1 or ns == 1:
-                        c.evp_peer_connect(1, exports[(r + 1) % R])
-                else:                            # any cartesian layout: by rank
-                    nbrs = c.evp_peer_ranks()
-                    assert r not in nbrs and 1 <= len(nbrs) <= 8
-                    for nr in nbrs:
-                        c.evp_peer_connect_rank(nr, exports[nr])
-                assert c.evp_get_info("resident_peer") == 1
-                assert c.evp_get_info("resident_peer_fine") == (0 if os.environ.get("CICE4_AMD_PEER_COARSE") == "1" else 1)
-                bar.wait(timeout=120)
             else:
                 c.evp_set_option("resident", 0)
                 if skew_k:
@@ -84,12 +74,36 @@ def run_ranks(gg, R, mode, ndte, dt, ns=0, seed=31, cover="patchy", overlap=0, s
                         c.evp_set_option("skew_min_cells", min_cells)
                     c.evp_set_option("skew_levels", skew_k)
                     assert c.evp_get_info("skew") == 1
+                    # the sweep in front of every refresh as two launches: the edge segments, followed by the refresh, on
+                    # the main stream; the interior beside them on a second one (off by default: on one GPU it costs more
+                    # than it hides, bench.py --gpus N decides by timing)
                     if split is not None:
                         c.evp_set_option("skew_split", split)
-                    assert c.evp_get_info("skew_trim_ext") == 1
+                        assert c.evp_get_info("skew_split") == split
+                    if ns not in (3, 4):     # (no tile lists under a fold: Evp::can_trim)
+                        assert c.evp_get_info("skew_trim_ext") == 1    # extension rows trimmed to what the next sweeps need
                 else:
                     c.evp_set_option("skew", 0)
+            if setup is not None:
+                setup(c, r, R)
             if mode == "peer":
+                exports[r] = c.evp_peer_export()
+                bar.wait(timeout=120)
+                if by_side:
+                    assert npx == 1 and blocks == (1, 1) and block_map is None
+                    if r > 0 or ns == 1:
+                        c.evp_peer_connect(0, exports[(r - 1) % R])
+                    if r < R - 1 or ns == 1:
+                        c.evp_peer_connect(1, exports[(r + 1) % R])
+                else:
+                    nbrs = c.evp_peer_ranks()
+                    assert r not in nbrs and 1 <= len(nbrs) <= 8
+                    for nr in nbrs:
+                        c.evp_peer_connect_rank(nr, exports[nr])
+                assert c.evp_get_info("resident_peer") == 1
+                # what the neighbour writes or polls is fine-grained device memory (coherent across devices during a launch)
+                assert c.evp_get_info("resident_peer_fine") == (0 if os.environ.get("CICE4_AMD_PEER_COARSE") == "1" else 1)
+                bar.wait(timeout=120)
                 # R loops on ONE device wait for each other, and a copy stream of one rank may share a hardware queue with the
                 # main stream of another: no rank's loop may start while another rank's uploads are still queued (on a node
                 # every rank has a device, and queues, of its own).  Same entry points as cice_evp, a barrier in between.
@@ -101,6 +115,8 @@ def run_ranks(gg, R, mode, ndte, dt, ns=0, seed=31, cover="patchy", overlap=0, s
                 assert c.evp_get_info("resident_peer") == 1, "the cross-rank loop timed out and fell back"
             else:
                 c.evp(dt, s)
+            if check is not None:
+                check(c, r, R)
             if info is not None and r == 0:
                 for k in ("fused", "skew", "skew_levels", "last_launches"):
                     info[k] = c.evp_get_info(k)

@@ -11,6 +11,7 @@ import pytest
 
 from cice4_amd import lib, synth
 from conftest import relerr, single_block_domain, TOL_EXP
+import ranks_case
 
 pytestmark = pytest.mark.gpu
 
@@ -466,16 +467,6 @@ def test_multi_level_halo_resident_on_device(monkeypatch, selfcomm):
         assert np.array_equal(got[:, untouched], np.ascontiguousarray(inside.transpose(1, 0, 2, 3)).reshape(nlev, -1)[:, untouched])
 
 
-def _owned(dom, f):
-    """global physical field from the OWNED rows of (possibly overlapping) slab blocks"""
-    g = np.zeros((dom["nyg"], dom["nxg"]))
-    for b in range(dom["nblocks"]):
-        r0 = dom["j0"][b] + (dom["own_jlo"][b] - dom["jlo"][b])
-        nr = dom["own_jhi"][b] - dom["own_jlo"][b] + 1
-        g[r0:r0 + nr, :] = f[b, dom["own_jlo"][b] - 1:dom["own_jhi"][b], dom["ilo"][b] - 1:dom["ihi"][b]]
-    return g
-
-
 @pytest.mark.parametrize("overlap,selfcomm,skew_k", [(0, False, 0), (1, False, 0), (2, False, 0), (4, False, 0), (7, False, 0),
                                                      (4, True, 0), (6, True, 0), (7, True, 0),
                                                      (8, False, 4), (8, True, 4), (12, True, 4), (6, True, 3)])
@@ -511,7 +502,7 @@ def test_wide_halo_slabs_equal_single_domain(orc, monkeypatch, overlap, selfcomm
     one = dict(nxg=nxg, nyg=nyg, nblocks=1, j0=[0], jlo=dom1["jlo"], jhi=dom1["jhi"], own_jlo=dom1["jlo"],
                own_jhi=dom1["jhi"], ilo=dom1["ilo"], ihi=dom1["ihi"])
     for k in ("uvel", "vvel", "divu", "shear", "strength", "strocnxT", "strocnyT", "strintx", "prs_sig") + synth.SIG_NAMES:
-        assert np.array_equal(_owned(dom, s[k]), _owned(one, s1[k])), (overlap, selfcomm, skew_k, k)
+        assert np.array_equal(ranks_case.owned(dom, s[k]), ranks_case.owned(one, s1[k])), (overlap, selfcomm, skew_k, k)
     nt, nu = c.evp_active_cells()
     c1.evp_init(grid1, ndte=NDTE, krdg_partic=0, krdg_redist=0)
     s1b = synth.evp_state(grid1, dom1, seed=31, cover="patchy")
@@ -519,9 +510,6 @@ def test_wide_halo_slabs_equal_single_domain(orc, monkeypatch, overlap, selfcomm
     nt1, nu1 = c1.evp_active_cells()
     assert nu == nu1                                # overlap rows are not counted twice
     assert nt1 <= nt <= nt1 + nb * (nxg + 2)        # T lists: each block also lists its N/E ghost ring
-
-
-_LINK = [1000]
 
 
 @pytest.mark.parametrize("mode,R,nyg", [("classic", 2, 72), ("peer", 2, 72), ("peer", 3, 72), ("peer", 2, 16), ("slabs4", 2, 72),
@@ -542,7 +530,6 @@ def test_ranks_in_one_process(orc, mode, R, nyg):
                subcycles per launch and, "sweep", K subcycles per sweep between the refreshes (K = 3, "sweep4": K = 4 with
                H = 8 -- what bench.auto_overlap picks -- and H = 4); the sweep in front of a refresh is split into edge
                and interior launches, the refresh overlapping the interior ("nosplit": the one-launch form)."""
-    import threading
     nxg = 96
     ns = 1 if mode == "peer-cyclic" else 0
     c1 = lib.Context()
@@ -554,80 +541,18 @@ def test_ranks_in_one_process(orc, mode, R, nyg):
     orc.set_evp_parameters(DT, NDTE, False); orc.set_strength_parameters(1, 0, 0, 4.0)
     orc.evp(orc.make_domain(dom1, grid1), s1)
     orc.set_strength_parameters()
-    _LINK[0] += 1
-    link = _LINK[0]
-    bar = threading.Barrier(R)
-    exports, out, errs = [None] * R, [None] * R, []
-
-    def rank_fn(r):
-        try:
-            c = lib.Context(device=0); c.sync()
-            bar.wait(timeout=60)         # (every rank's main stream before anybody's copy streams: tests/ranks_case.py)
-            if mode.startswith("slabs"):
-                H = int(mode[5])
-                dom = c.domain_create_slabs(nxg, nyg, R, ew=1, ns=0, rank=r, nranks=R, overlap=H)
-            else:
-                dom = c.domain_create(nxg, nyg, nxg, nyg // R, ew=1, ns=ns, rank=r, npx=1, npy=R)
-            assert dom["nblocks"] == 1 and dom["nsend"] >= 1
-            c.comm_init_local(link, r, R)
-            grid = synth.block_fields(gg, dom, ns_cyclic=(ns == 1))
-            s = synth.evp_state(grid, dom, seed=31, cover="patchy")
-            c.evp_init(grid, ndte=NDTE, krdg_partic=0, krdg_redist=0)
-            if mode.startswith("peer"):
-                c.evp_set_option("resident_peer_share", R)
-                exports[r] = c.evp_peer_export()
-                bar.wait(timeout=60)
-                if r > 0 or ns == 1:
-                    c.evp_peer_connect(0, exports[(r - 1) % R])
-                if r < R - 1 or ns == 1:
-                    c.evp_peer_connect(1, exports[(r + 1) % R])
-                assert c.evp_get_info("resident_peer") == 1
-                # what the neighbour writes or polls is fine-grained device memory (coherent across devices during a launch)
-                assert c.evp_get_info("resident_peer_fine") == (0 if os.environ.get("CICE4_AMD_PEER_COARSE") == "1" else 1)
-                bar.wait(timeout=60)
-            else:
-                c.evp_set_option("resident", 0)
-                if "sweep" in mode:
-                    c.evp_set_option("skew_min_cells", 0); c.evp_set_option("skew_levels", 4 if "sweep4" in mode else 3)
-                    assert c.evp_get_info("skew") == 1
-                    # the sweep in front of every refresh runs as two launches: the edge segments, followed by the
-                    # refresh, on the main stream; the interior beside them on a second one (round 4)
-                    # (off by default -- on one GPU it costs more than it hides; bench.py --gpus N decides by timing)
-                    c.evp_set_option("skew_split", 0 if mode.endswith("nosplit") else 1)
-                    assert c.evp_get_info("skew_split") == (0 if mode.endswith("nosplit") else 1)
-                    assert c.evp_get_info("skew_trim_ext") == 1    # extension rows trimmed to what the next sweeps need
-                else:
-                    c.evp_set_option("skew", 0)
-            if mode.startswith("peer"):   # (no rank's loop starts while another rank's uploads are queued: tests/ranks_case.py)
-                c.evp_upload(s); bar.wait(timeout=120)
-                c.evp_step(DT); bar.wait(timeout=120)
-                c.evp_download(s)
-                assert c.evp_get_info("resident_peer") == 1, "the cross-rank loop timed out and fell back"
-            else:
-                c.evp(DT, s)
-            out[r] = (dom, s)
-            bar.wait(timeout=120)        # nobody frees buffers a neighbour may still be writing to
-        except BaseException as e:       # noqa: BLE001 -- reported by the main thread
-            errs.append((r, repr(e)))
-            bar.abort()
-
-    th = [threading.Thread(target=rank_fn, args=(r,)) for r in range(R)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(300)
-    assert not errs, errs
+    if not mode.startswith("slabs"):
+        kind, kw = mode.split("-")[0], dict(ns=ns, by_side=True)     # (by side: the call that can name the same rank twice)
+    elif "sweep" in mode:
+        kind, kw = "slabs", dict(overlap=int(mode[5]), skew_k=4 if "sweep4" in mode else 3, min_cells=0,
+                                 split=0 if mode.endswith("nosplit") else 1)
+    else:
+        kind, kw = "slabs", dict(overlap=int(mode[5]))
+    out = ranks_case.run_ranks(gg, R, kind, NDTE, DT, seed=31, cover="patchy", timeout=300, **kw)
     one = dict(nxg=nxg, nyg=nyg, nblocks=1, j0=[0], jlo=dom1["jlo"], jhi=dom1["jhi"], own_jlo=dom1["jlo"],
                own_jhi=dom1["jhi"], ilo=dom1["ilo"], ihi=dom1["ihi"])
     for k in ("uvel", "vvel", "divu", "shear", "strength", "strocnxT", "strocnyT", "strintx", "prs_sig") + synth.SIG_NAMES:
-        want = _owned(one, s1[k])
-        got = np.zeros_like(want)
-        for r in range(R):
-            dom, s = out[r]
-            part = _owned(dom, s[k])
-            rows = slice(int(dom["j0"][0] + dom["own_jlo"][0] - dom["jlo"][0]),
-                         int(dom["j0"][0] + dom["own_jhi"][0] - dom["jlo"][0]) + 1)
-            got[rows] = part[rows]
+        want, got = ranks_case.owned(one, s1[k]), ranks_case.assemble(out, k, nxg, nyg)
         assert np.array_equal(got, want), (mode, R, k, np.argwhere(got != want)[:5])
     # ghost rows a neighbour owns are current after evp(dt) (the last exchange of the loop, ice_dyn_evp.F90:397-402)
     if not mode.startswith("slabs"):
@@ -653,7 +578,6 @@ def test_cartesian_layouts_of_ranks_in_one_process(orc, mode, npx, npy, nxg, nyg
     cyclic grid: the eastern and the western neighbour are the same rank) against the per-subcycle message path ("classic")
     and the checker on the whole grid, bit for bit; blocks narrower and shorter than a tile; SEVERAL blocks per rank
     (`blocks`: tiles numbered block by block, ghost cells between a rank's own blocks forwarded on the device)."""
-    import ranks_case
     R = npx * npy
     gg = synth.global_grid(nxg, nyg, perturb=0.15, land_frac=0.05, seed=31)
     c1 = lib.Context()
@@ -667,7 +591,7 @@ def test_cartesian_layouts_of_ranks_in_one_process(orc, mode, npx, npy, nxg, nyg
     one = dict(nxg=nxg, nyg=nyg, nblocks=1, j0=[0], jlo=dom1["jlo"], jhi=dom1["jhi"], own_jlo=dom1["jlo"],
                own_jhi=dom1["jhi"], ilo=dom1["ilo"], ihi=dom1["ihi"])
     for k in ("uvel", "vvel", "divu", "shear", "strength", "strocnxT", "strocnyT", "strintx", "prs_sig") + synth.SIG_NAMES:
-        want, got = _owned(one, s1[k]), ranks_case.assemble_blocks(out, k, nxg, nyg)
+        want, got = ranks_case.owned(one, s1[k]), ranks_case.assemble_blocks(out, k, nxg, nyg)
         assert np.array_equal(got, want), (mode, npx, npy, k, np.argwhere(got != want)[:5].tolist())
 
 
@@ -678,7 +602,6 @@ def test_ranks_with_an_eliminated_land_block(orc, mode):
     The ghost cells that face the eliminated block have no producer and keep the fill value of the first halo update; the
     cross-rank one-launch loop (several blocks per rank, neighbours by rank) and the per-subcycle message path against the
     checker on the whole grid, bit for bit on every ocean cell."""
-    import ranks_case
     nxg, nyg, bs, R = 96, 72, 24, 3
     gg = synth.global_grid(nxg, nyg, perturb=0.15, land_frac=0.03, seed=31)
     gg["hm"][24:48, 48:72] = 0.0                         # block (ib = 2, jb = 1): all land
@@ -696,7 +619,7 @@ def test_ranks_with_an_eliminated_land_block(orc, mode):
                own_jhi=dom1["jhi"], ilo=dom1["ilo"], ihi=dom1["ihi"])
     keep = np.ones((nyg, nxg), bool); keep[24:48, 48:72] = False
     for k in ("uvel", "vvel", "divu", "shear", "strength", "strintx", "prs_sig") + synth.SIG_NAMES:
-        want, got = _owned(one, s1[k]), ranks_case.assemble_blocks(out, k, nxg, nyg)
+        want, got = ranks_case.owned(one, s1[k]), ranks_case.assemble_blocks(out, k, nxg, nyg)
         assert np.array_equal(got[keep], want[keep]), (mode, k, np.argwhere((got != want) & keep)[:5].tolist())
     assert np.abs(s1["uvel"]).max() > 0.01
 
@@ -715,7 +638,6 @@ def test_tripole_grid_cut_into_slabs(ctx, ns, mode, R, nyg):
     cross-rank loop WITH the fold inside (its top-row tiles exchange their raw velocities among themselves, as on one rank),
     the others the plain cross-rank loop.  Against the one-block domain through one launch per subcycle (pinned to the compiled reference
     on such a grid), bit for bit on every owned cell; ocean and patchy ice up to the fold."""
-    import threading
     nxg = 96
     dom1 = ctx.domain_create(nxg, nyg, nxg, nyg, ew=1, ns=ns)
     gg = synth.global_grid(nxg, nyg, perturb=0.15, land_frac=0.05, seed=31 + ns, land_rows=0)
@@ -723,79 +645,32 @@ def test_tripole_grid_cut_into_slabs(ctx, ns, mode, R, nyg):
     s1 = synth.evp_state(grid1, dom1, seed=31, cover="patchy")
     s1, _ = _evp_with(ctx, grid1, s1, NDTE, False, resident=0, skew=0, skew_fold=0)
     assert np.abs(s1["uvel"][0, -3:]).max() > 1e-4
+    peer = mode.startswith("peer")
     peer_w = int(mode[6:]) if mode.startswith("peer-W") else 0
-    if peer_w:
-        mode = "peer"
-    H = 0 if mode == "peer" else int(mode[5])
-    _LINK[0] += 1
-    link = _LINK[0]
-    bar = threading.Barrier(R)
-    out, errs, exports = [None] * R, [], [None] * R
+    H = 0 if peer else int(mode[5])
+    # "sweep4": K = 4 does not divide the 6 subcycles between refreshes (4 + 1 + 1 / 4 + 2)
+    K = 0 if "sweep" not in mode else int(mode[-1]) if mode[-1].isdigit() else 3
 
-    def rank_fn(r):
-        try:
-            c = lib.Context(device=0); c.sync()
-            bar.wait(timeout=120)        # (every rank's main stream before anybody's copy streams: tests/ranks_case.py)
-            if mode == "peer":
-                dom = c.domain_create(nxg, nyg, nxg, nyg // R, ew=1, ns=ns, rank=r, npx=1, npy=R)
-            else:
-                dom = c.domain_create_slabs(nxg, nyg, R, ew=1, ns=ns, rank=r, nranks=R, overlap=H)
-            assert dom["nblocks"] == 1 and dom["nsend"] >= 1
-            c.comm_init_local(link, r, R)
-            grid = synth.block_fields(gg, dom, ew_cyclic=True, north_ocean=True)
-            s = synth.evp_state(grid, dom, seed=31, cover="patchy")
-            c.evp_init(grid, ndte=NDTE, krdg_partic=0, krdg_redist=0)
-            if mode == "peer":
-                c.evp_set_option("resident_peer_share", R)
-                if peer_w:
-                    c.evp_set_option("resident_waves", peer_w)
-                exports[r] = c.evp_peer_export()
-                bar.wait(timeout=120)
-                nbrs = c.evp_peer_ranks()
-                assert nbrs == [x for x in (r - 1, r + 1) if 0 <= x < R], nbrs      # (nobody is the top slab's northern neighbour)
-                for nr in nbrs:
-                    c.evp_peer_connect_rank(nr, exports[nr])
-                assert c.evp_get_info("resident_peer") == 1
-                bar.wait(timeout=120)
-            else:
-                c.evp_set_option("resident", 0)
-            if mode == "peer":
-                pass
-            elif "sweep" in mode:      # "sweep4": K = 4 does not divide the 6 subcycles between refreshes (4 + 1 + 1 / 4 + 2)
-                c.evp_set_option("skew_min_cells", 0); c.evp_set_option("skew_levels", int(mode[-1]) if mode[-1].isdigit() else 3)
-                assert c.evp_get_info("skew_fold" if r == R - 1 else "skew") == 1, r
-            else:
-                c.evp_set_option("skew", 0); c.evp_set_option("skew_fold", 0)
-            if mode == "peer":      # (no rank's loop starts while another rank's uploads are queued: tests/ranks_case.py)
-                c.evp_upload(s); bar.wait(timeout=120)
-                c.evp_step(DT); bar.wait(timeout=120)
-                c.evp_download(s)
-                assert c.evp_get_info("resident_peer") == 1 and c.evp_get_info("last_launches") == 1, "the cross-rank loop fell back"
-            else:
-                c.evp(DT, s)
-            out[r] = (dom, s)
-            bar.wait(timeout=120)
-        except BaseException as e:       # noqa: BLE001 -- reported by the main thread
-            errs.append((r, repr(e)))
-            bar.abort()
+    def setup(c, r, R):
+        if peer:
+            if peer_w:
+                c.evp_set_option("resident_waves", peer_w)
+            assert c.evp_peer_ranks() == [x for x in (r - 1, r + 1) if 0 <= x < R]    # (nobody is the top slab's northern neighbour)
+        elif K:
+            assert c.evp_get_info("skew_fold" if r == R - 1 else "skew") == 1, r
+        else:
+            c.evp_set_option("skew_fold", 0)
 
-    th = [threading.Thread(target=rank_fn, args=(r,)) for r in range(R)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(300)
-    assert not errs, errs
+    def check(c, r, R):
+        if peer:
+            assert c.evp_get_info("resident_peer") == 1 and c.evp_get_info("last_launches") == 1, "the cross-rank loop fell back"
+
+    out = ranks_case.run_ranks(gg, R, "peer" if peer else "slabs", NDTE, DT, ns=ns, seed=31, cover="patchy", overlap=H, skew_k=K,
+                               min_cells=0, timeout=300, setup=setup, check=check)
     one = dict(nxg=nxg, nyg=nyg, nblocks=1, j0=[0], jlo=dom1["jlo"], jhi=dom1["jhi"], own_jlo=dom1["jlo"],
                own_jhi=dom1["jhi"], ilo=dom1["ilo"], ihi=dom1["ihi"])
     for k in ("uvel", "vvel", "divu", "shear", "strength", "strocnxT", "strocnyT", "strintx", "prs_sig") + synth.SIG_NAMES:
-        want = _owned(one, s1[k])
-        got = np.zeros_like(want)
-        for r in range(R):
-            dom, s = out[r]
-            part = _owned(dom, s[k])
-            rows = slice(int(dom["j0"][0] + dom["own_jlo"][0] - dom["jlo"][0]),
-                         int(dom["j0"][0] + dom["own_jhi"][0] - dom["jlo"][0]) + 1)
-            got[rows] = part[rows]
+        want, got = ranks_case.owned(one, s1[k]), ranks_case.assemble(out, k, nxg, nyg)
         assert np.array_equal(got, want), (ns, mode, R, k, np.argwhere(got != want)[:5])
     # the ghost row beyond the fold, as the last halo update of the loop leaves it (a wide-halo domain hands back its
     # owned rows only)
@@ -827,7 +702,7 @@ def test_tripole_grid_cut_into_slabs_on_one_rank(ctx, ns, nb, overlap):
     one = dict(nxg=nxg, nyg=nyg, nblocks=1, j0=[0], jlo=dom1["jlo"], jhi=dom1["jhi"], own_jlo=dom1["jlo"],
                own_jhi=dom1["jhi"], ilo=dom1["ilo"], ihi=dom1["ihi"])
     for k in ("uvel", "vvel", "divu", "shear", "strength", "strocnxT", "strocnyT", "strintx", "prs_sig") + synth.SIG_NAMES:
-        got, want = _owned(dom, s[k]), _owned(one, s1[k])
+        got, want = ranks_case.owned(dom, s[k]), ranks_case.owned(one, s1[k])
         assert np.array_equal(got, want), (ns, nb, overlap, k, np.argwhere(got != want)[:5].tolist())
 
 
