@@ -887,6 +887,7 @@ int cice_evp_get_info(cice_ctx* ctx, const char* key, int* value) {
   else if (!std::strcmp(key, "fused_waves")) *value = c_->evp->fused_waves();
   else if (!std::strcmp(key, "skew")) *value = c_->evp->can_skew() || c_->evp->can_skew_fold() ? 1 : 0;
   else if (!std::strcmp(key, "skew_fold")) *value = !c_->evp->can_skew() && c_->evp->can_skew_fold() ? 1 : 0;
+  else if (!std::strcmp(key, "skew_joined")) *value = c_->evp->skew_joined() ? 1 : 0;
   else if (!std::strcmp(key, "skew_levels")) *value = c_->evp->skew_levels();
   else if (!std::strcmp(key, "skew_subs")) *value = c_->evp->skew_subs(c_->evp->skew_levels());
   else if (!std::strcmp(key, "skew_pairs")) *value = c_->evp->pairs_ok() ? 1 : 0;
@@ -1851,6 +1852,15 @@ int cice_debug_skew_layout(int K, int S, int ncol, int cyclic, int* strips) {
       return shift;
     }
   return -1;
+}
+
+// test aid, no device needed: the cell map of the image a one-task domain of several blocks is joined into for the sweeps
+long long cice_debug_join_map(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t* map, long long cap) {
+  try {
+    return cice::join_map_debug(nxg, nyg, bsx, bsy, ew, ns, map, cap);
+  } catch (...) {
+    return -2;
+  }
 }
 
 // test aid, no device needed: one strip's step of the measured balancing of the sweep's segments (cice::balance_strip)

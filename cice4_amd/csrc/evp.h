@@ -8,6 +8,7 @@
 #include "common.h"
 #include "domain.h"
 #include "halo.h"
+#include "join.h"
 
 namespace cice {
 
@@ -68,6 +69,8 @@ class Evp {
   bool resident_dense() const; // three 4-wavefront workgroups per CU instead of one workgroup per CU
   bool granules_in_use() const { return can_reside() && !halo.multi_rank() && granules_on() && !resident_dense(); }   // the one-launch loop hands its edge velocities on as data-tagged granules
   bool can_skew() const;     // K subcycles per sweep (k_subcycle_skew) on this domain
+  bool can_join() const;     // ... of several blocks: the sweeps run on a joined image of them (join.h)
+  bool skew_joined() const { return can_join() && can_skew(); }
   bool can_split() const;    // ... and the sweep in front of a wide-halo refresh as edge + interior launches
   bool skew_rows_on() const { return (skew_gen_pct > 0 || skew_fill_on() || balance_on()) && skew_seg_opt == 0; }   // segments of unequal length (build_skew_rows)
   bool skew_fill_on() const;
@@ -237,6 +240,15 @@ class Evp {
   bool pairs_on = true, in_pairs = false, copies_identical = false;
   void to_pairs();
   void to_planes();
+  // sweeps on a joined image of the blocks (join.h): what sizes a sweep sees the image as a one-block domain
+  struct SweepGeom { int nx, ny, nb; bool cyc; size_t n; };
+  SweepGeom sg() const;
+  JoinImage img;
+  bool join_on = true, in_image = false, packed_joined = false, img_out = false;   // img_out: the image holds what the sweep that ends evp(dt) leaves beside the state
+  bool img_pairs() const;    // the image's copies of the state are in the pair layout
+  void img_ensure();         // allocations and the grid's planes (outside any capture)
+  void to_image();
+  void to_blocks();
   // in
   DevBuf<double> aice, vice, vsno, aice0, aicen, vicen, strairxT, strairyT, uocn, vocn, ss_tltx,
       ss_tlty;

@@ -3058,6 +3058,10 @@ void Evp::set_option(const char* key, int value) {
     res_w_opt = value;
   } else if (!std::strcmp(key, "skew")) {          // K subcycles per sweep (k_subcycle_skew) where the domain allows
     skew_on = value != 0;
+  } else if (!std::strcmp(key, "skew_join")) {     // one-task domains of several blocks: sweeps on a joined image of them (join.h)
+    join_on = value != 0;
+    skew_packed = false;
+    skew_rows_key[0] = -1;
   } else if (!std::strcmp(key, "skew_levels")) {   // 0 = auto
 #ifdef CICE4_AMD_EXPERIMENTS
     CICE_REQUIRE(value == 0 || value == 2 || value == 3 || value == 4 || value == 5 || value == 6 || value == 8,
@@ -3175,6 +3179,7 @@ void Evp::init(const cice_evp_config& c, const cice_evp_grid& g) {
     }
     fwd_is_ew_wrap = ok;
   }
+  img.init(dom, stream);   // the blocks as one image for the sweep kernel, where they tile the grid (join.h)
   // the eight read-only inputs of the momentum equation share one allocation (k_subcycle_skew: one base pointer)
   uarena.alloc(8 * n);
   {
@@ -3439,27 +3444,34 @@ void Evp::prepare(double dt) {
 
 // the sweep kernel's interleaved read-only inputs (SkewArgs::uar4 / hnhe / msk) from this step's work arrays
 void Evp::skew_pack() {
-  if (uar4.n < 8 * n) {
-    uar4.alloc(8 * n);
-    skew_msk.alloc(n);
-    hnhe.alloc(2 * n);
-    hipLaunchKernelGGL(k_skew_pack_grid, grid1(n), dim3(256), 0, stream, n, (const double*)HTN.p, (const double*)HTE.p, hnhe.p);
+  const bool joined = can_join();
+  const SweepGeom g = sg();
+  if (joined) {           // the same inputs in image geometry, gathered while they are packed
+    img_ensure();
+    img.pack_inputs(stream, uarena.p, icetmask.p, iceumask.p, strength.p);
+  } else {
+    if (uar4.n < 8 * n) {
+      uar4.alloc(8 * n);
+      skew_msk.alloc(n);
+      hnhe.alloc(2 * n);
+      hipLaunchKernelGGL(k_skew_pack_grid, grid1(n), dim3(256), 0, stream, n, (const double*)HTN.p, (const double*)HTE.p, hnhe.p);
+    }
+    hipLaunchKernelGGL(k_skew_pack, grid1(n), dim3(256), 0, stream, n, (const double*)uarena.p, (const int32_t*)icetmask.p,
+                       (const int32_t*)iceumask.p, uar4.p, skew_msk.p);
   }
-  hipLaunchKernelGGL(k_skew_pack, grid1(n), dim3(256), 0, stream, n, (const double*)uarena.p, (const int32_t*)icetmask.p,
-                     (const int32_t*)iceumask.p, uar4.p, skew_msk.p);
   // rows with anything to compute, per column strip (this step's masks)
   rowact_strips = 0;
   if (rowact_on()) {
-    const int K = skew_levels(), rows = dom.ny_block - 2;
+    const int K = skew_levels(), rows = g.ny - 2;
     int shift = 0;
     const int strips = skew_strips(K, &shift);
-    const size_t want = (size_t)dom.nblocks() * strips * rows;
+    const size_t want = (size_t)g.nb * strips * rows;
     if (rowact.n < want) rowact.alloc(want);
-    hipLaunchKernelGGL(k_skew_rowact, dim3((unsigned)((rows + 3) / 4), (unsigned)strips, (unsigned)dom.nblocks()), dim3(256), 0,
-                       stream, K, strips, shift, dom.nx_block, dom.ny_block, 0, (const int32_t*)blk.p,
-                       (const int32_t*)skew_msk.p, rowact.p);
+    hipLaunchKernelGGL(k_skew_rowact, dim3((unsigned)((rows + 3) / 4), (unsigned)strips, (unsigned)g.nb), dim3(256), 0,
+                       stream, K, strips, shift, g.nx, g.ny, 0, (const int32_t*)(joined ? img.blk.p : blk.p),
+                       (const int32_t*)(joined ? img.msk.p : skew_msk.p), rowact.p);
     if (run_next.n < want) { run_next.alloc(want); run_end.alloc(want); }
-    const int ns = dom.nblocks() * strips;
+    const int ns = g.nb * strips;
     hipLaunchKernelGGL(k_skew_runs, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, stream, ns, rows, 3 * K,
                        (const unsigned char*)rowact.p, run_next.p, run_end.p);
     rowact_strips = strips;
@@ -3467,6 +3479,7 @@ void Evp::skew_pack() {
     rowact_host_stale = true;
   }
   skew_packed = true;
+  packed_joined = joined;
 }
 
 int Evp::resident_map() {
@@ -3750,11 +3763,61 @@ void Evp::launch_subcycle_pair(int ksub) {
 // Small grids keep k_subcycle2 / the resident loop: a sweep needs rows to amortise its 2(K-1) + 2K - 1 extra steps.
 bool Evp::can_skew() const {
   static const bool env_off = [] { const char* e = std::getenv("CICE4_AMD_SKEW"); return e && e[0] == '0'; }();
-  if (!skew_on || env_off || !can_fuse() || !(derive_ok && derive_on)) return false;
-  if (n * 8 * 14 >= (1ull << 32)) return false;   // the kernel reaches the 14 planes of the state by 32-bit offsets
-  const long long cells = (long long)dom.nblocks() * (dom.nx_block - 2) * (dom.ny_block - 2);
+  if (!skew_on || env_off || !(can_fuse() || can_join()) || !(derive_ok && derive_on)) return false;
+  const SweepGeom g = sg();
+  if (g.n * 8 * 14 >= (1ull << 32)) return false;   // the kernel reaches the 14 planes of the state by 32-bit offsets
+  const long long cells = (long long)g.nb * (g.nx - 2) * (g.ny - 2);
   if (cells < skew_min_cells) return false;
   return skew_strips(skew_levels(), nullptr) > 0;   // (0: no column layout passes skew_layout_ok for this width)
+}
+
+// ---- sweeps on a joined image of the blocks (join.h) ---------------------------------------------------------------------
+// A one-task domain cut into several blocks cannot give the sweep kernel the full-width block it wants -- but where its
+// blocks tile the whole grid, an image of them can: (nxg + 2) x (nyg + 2) cells, one pseudo-block.  launch_range() gathers
+// the state into the image before the first sweep of a range (to_image: both ping-pong copies, in the pair layout where
+// the one-block sweep of the same grid would use it), runs the sweeps there -- everything that sizes a sweep sees sg() --
+// and scatters it back before anything that needs blocks (to_blocks).  The read-only inputs are packed in image geometry
+// once per prepare() (skew_pack), HTN | HTE once per grid.  Not for domains the two-subcycle kernel or a fold serves:
+// those keep their paths.
+bool Evp::can_join() const {
+  static const bool env_off = [] { const char* e = std::getenv("CICE4_AMD_SKEW_JOIN"); return e && e[0] == '0'; }();
+  return join_on && !env_off && SKEW_WIDE && img.g.ok && fuse_on && !halo.multi_rank() && !halo.has_fold();
+}
+
+Evp::SweepGeom Evp::sg() const {
+  const bool cyc = dom.ew == BND_CYCLIC;
+  if (can_join()) return {img.g.nx, img.g.ny, 1, cyc, img.g.n};
+  return {dom.nx_block, dom.ny_block, dom.nblocks(), cyc, n};
+}
+
+// the pair layout of the image's state: where the one-block sweep of the same grid has it (pairs_ok)
+bool Evp::img_pairs() const { return pairs_ok(); }
+
+void Evp::img_ensure() {
+  img.alloc();
+  if (!img.grid_done) img.pack_grid(stream, HTN.p, HTE.p, tarear.p);
+}
+
+void Evp::to_image() {
+  if (in_image) return;
+  const bool pairs = img_pairs();
+  img.join_state(stream, st[cur].p, cur, pairs);
+  ++loop_launches;
+  in_image = true;
+  in_pairs = pairs;
+  img_out = false;
+}
+
+void Evp::to_blocks() {
+  if (!in_image) return;
+  img.split_state(stream, st[cur].p, cur, in_pairs, icetmask.p, iceumask.p);
+  ++loop_launches;
+  if (img_out) {
+    double* const o[9] = {divu.p, rdg_conv.p, rdg_shear.p, shear.p, prs_sig.p, strintx.p, strinty.p, strocnx.p, strocny.p};
+    img.split_out(stream, o, icetmask.p, iceumask.p);
+    ++loop_launches;
+  }
+  in_image = in_pairs = img_out = false;
 }
 
 int Evp::skew_levels() const { return skew_k_opt ? skew_k_opt : 4; }
@@ -3836,7 +3899,7 @@ bool evp_skew_layout_ok(int K, int S, int ncol, int shift, bool cyc) { return sk
 // (ihi, G, ilo) must not lie where a strip's east rim -- or, S > 1, the two columns neighbouring wavefronts share --
 // would need one lane more.
 int Evp::skew_strips(int K, int* shift_out) const {
-  const int ncol = dom.nx_block - 2, S = skew_subs(K), txw = 62 * S + 2, ownw = txw - 2 * K;
+  const int ncol = sg().nx - 2, S = skew_subs(K), txw = 62 * S + 2, ownw = txw - 2 * K;
   int& cached = strips_cache[K][S == 3];
   int& cshift = strips_cache_shift[K][S == 3];
   if (cached == 0) {
@@ -3877,14 +3940,14 @@ int Evp::skew_blocks(int K) const {
 
 // rows a workgroup owns: as many workgroups as the chip holds at once (one round), segments not shorter than 4K rows
 int Evp::skew_seg_rows(int K) const {
-  const int rows = dom.ny_block - 2;
+  const int rows = sg().ny - 2;
   if (skew_seg_opt) return std::min(skew_seg_opt, rows);
   int ncu = 256, dev = 0;
   if (hipGetDevice(&dev) == hipSuccess) {
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
   }
-  const long long strips = (long long)skew_strips(K, nullptr) * dom.nblocks();
+  const long long strips = (long long)skew_strips(K, nullptr) * sg().nb;
   long long nseg = (long long)ncu * skew_blocks(K) / std::max(1LL, strips);
   nseg = std::max(1LL, std::min(nseg, (long long)std::max(1, rows / (4 * K))));
   return (int)((rows + nseg - 1) / nseg);
@@ -3938,7 +4001,7 @@ void Evp::build_skew_rows(int K, int tiles_x, int tiles_y, int nblocks, int seg_
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
   }
   const int per_blk = tiles_x * tiles_y, nt = per_blk * nblocks, per_xcd = std::max(1, ncu / 8);
-  const int rows = dom.ny_block - 2, gens = std::max(1, skew_blocks(K));
+  const int rows = sg().ny - 2, gens = std::max(1, skew_blocks(K));
   const bool fill = skew_fill_on() && nblocks == 1;
   std::vector<int32_t> tab((size_t)2 * per_blk);
   rows_w.assign((size_t)per_blk, 1.0);
@@ -4026,7 +4089,7 @@ void Evp::bal_upload(hipStream_t s) {
 // Option "skew_balance" / CICE4_AMD_SKEW_BALANCE=0|1.
 bool Evp::balance_on() const {
   static const int env = [] { const char* e = std::getenv("CICE4_AMD_SKEW_BALANCE"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-  return (env >= 0 ? env == 1 : skew_balance != 0) && dom.nblocks() == 1;
+  return (env >= 0 ? env == 1 : skew_balance != 0) && sg().nb == 1;
 }
 
 // One strip's step of the measured balancing, as a pure function (Evp::balance_after_sweep; cice_debug_balance_strip for the
@@ -4128,7 +4191,7 @@ void Evp::balance_after_sweep(hipStream_t s) {
   CICE_HIP(hipStreamSynchronize(s));
   std::vector<long long> t(2 * g);
   CICE_HIP(hipMemcpy(t.data(), skew_dbg.p, t.size() * 8, hipMemcpyDeviceToHost));
-  const int rows = dom.ny_block - 2;
+  const int rows = sg().ny - 2;
   // the rows that hold ice, per strip (this step's masks: fetched once per loop that is measured)
   const bool have_act = rowact_on() && rowact_strips == ns && rowact.n >= (size_t)ns * rows;
   if (have_act && rowact_host_stale) {
@@ -4308,6 +4371,7 @@ static void launch_skew_kb(const SkewArgs& sa, bool last, bool damp, dim3 g, hip
 bool Evp::pairs_ok() const {
   static const bool env_off = [] { const char* e = std::getenv("CICE4_AMD_SKEW_PAIRS"); return e && e[0] == '0'; }();
   if (!pairs_on || env_off || !SKEW_WIDE) return false;
+  if (can_join()) return can_skew() && skew_levels() == 4 && skew_waves_per_simd(4) == 3 && dom.ew == BND_CYCLIC;   // (the image)
   return can_skew() && skew_levels() == 4 && skew_waves_per_simd(4) == 3 && fwd_is_ew_wrap && !halo.has_refresh() &&
          !halo.has_fold() && dom.overlap == 0;
 }
@@ -4335,14 +4399,14 @@ void Evp::skew_args(SkewArgs& sa, int K) {
   sa.a = make_args();
   sa.seg_rows = skew_seg_rows(K);
   sa.a.tiles_x = skew_strips(K, &sa.own_shift);
-  sa.a.tiles_y = ((dom.ny_block - 2) + sa.seg_rows - 1) / sa.seg_rows;
+  sa.a.tiles_y = ((sg().ny - 2) + sa.seg_rows - 1) / sa.seg_rows;
   sa.prio_rotate = skew_prio;
   {
     static const int deal = [] { const char* e = std::getenv("CICE4_AMD_SKEW_DEAL"); return e ? std::atoi(e) : 0; }();
     sa.level_deal = deal;
   }
   sa.rows = nullptr;
-  sa.fwd_rule = fwd_is_ew_wrap ? 1 : 0;
+  sa.fwd_rule = fwd_is_ew_wrap || in_image ? 1 : 0;   // (the image: its only ghost copies are the east-west wrap, if any)
   sa.dbg = nullptr;
   sa.stamps = nullptr;
   sa.phases = nullptr;
@@ -4354,6 +4418,23 @@ void Evp::skew_args(SkewArgs& sa, int K) {
   sa.uar4 = uar4.p;
   sa.hnhe = hnhe.p;
   sa.msk = skew_msk.p;
+  if (in_image) {   // the image as a one-block domain: its own planes of everything the kernel names
+    SubArgs& a = sa.a;
+    a.nx = img.g.nx; a.ny = img.g.ny; a.n = img.g.n; a.nblocks = 1; a.blk = img.blk.p;
+    a.ring_slot = nullptr; a.fwd = nullptr; a.carry_top = 0;
+    a.icetmask = nullptr; a.iceumask = nullptr;
+    a.HTN = img.HTN.p; a.HTE = img.HTE.p; a.tarear = img.tarear.p; a.strength = img.strength.p;
+    double* const o = img.out.p;
+    const size_t m = img.g.n;
+    a.divu = o; a.rdg_conv = o + m; a.rdg_shear = o + 2 * m; a.shear = o + 3 * m; a.prs_sig = o + 4 * m;
+    a.strintx = o + 5 * m; a.strinty = o + 6 * m; a.strocnx = o + 7 * m; a.strocny = o + 8 * m;
+    sa.st_in = img.st[cur].p;
+    sa.st_out = img.st[1 - cur].p;   // (the sweep that ends evp(dt) stores planes there: nothing reads that copy as pairs again)
+    sa.uar = nullptr;
+    sa.uar4 = img.uar4.p;
+    sa.hnhe = img.hnhe.p;
+    sa.msk = img.msk.p;
+  }
   sa.tiles = nullptr;
   sa.tile_first = sa.tile_count = 0;
   sa.rowact = rowact_on() && rowact_strips == sa.a.tiles_x && rowact_k == K ? rowact.p : nullptr;
@@ -4366,7 +4447,7 @@ void Evp::skew_launch(const SkewArgs& sa0, int K, bool last, int nt, hipStream_t
   const bool damp = sc.evp_damping != 0;
   const int WS = skew_waves_per_simd(K);
   SkewArgs sa = sa0;
-  if (in_pairs && !last) sa.st_out = st2[1 - cur].p;
+  if (in_pairs && !last && !in_image) sa.st_out = st2[1 - cur].p;
   switch (K * 10 + WS) {
     case 23: launch_skew_kb<2, 3>(sa, last, damp, g, s); break;
     case 33: launch_skew_kb<3, 3>(sa, last, damp, g, s); break;
@@ -4413,7 +4494,14 @@ void Evp::launch_subcycle_skew(int ksub, int K, bool flip_and_halo, hipStream_t 
   skew_launch(sa, K, ksub + K - 1 == sc.ndte, nt, on ? on : stream);
   if (measure) balance_after_sweep(on ? on : stream);
   if (in_pairs && ksub + K - 1 == sc.ndte) in_pairs = false;   // the last sweep of evp(dt) stores planes
-  if (flip_and_halo) after_subcycle(ksub + K - 1);
+  if (in_image) {            // the blocks' ghost cells are the split's business (to_blocks)
+    if (ksub + K - 1 == sc.ndte) img_out = true;
+    cur = 1 - cur;
+    ++flips;
+    copies_identical = false;
+  } else if (flip_and_halo) {
+    after_subcycle(ksub + K - 1);
+  }
 }
 
 // ---- the sweep in front of a wide-halo refresh: the rows the neighbours wait for FIRST ------------------------------
@@ -5623,7 +5711,8 @@ void Evp::launch_range(int ksub0, int nsub) {
   const bool skew = can_skew(), skew_fold = !skew && can_skew_fold();
   const int K = skew_levels();
   const bool trim = skew && can_trim(), split = trim && can_split();
-  const bool pairs = skew && !trim && split_probe == 0 && pairs_ok();
+  const bool joined = skew && can_join();
+  const bool pairs = skew && !joined && !trim && split_probe == 0 && pairs_ok();
   const int end = ksub0 + nsub - 1;
   for (int k = ksub0; k <= end;) {
     // a wide-halo refresh falls after subcycles that are multiples of `overlap`: a launch must not straddle one,
@@ -5637,6 +5726,7 @@ void Evp::launch_range(int ksub0, int nsub) {
     };
     if (skew && clear(K)) {
       const int kend = k + K - 1;
+      if (joined) to_image();
       if (pairs) to_pairs();
       if (split_probe > 0 && !in_capture && dom.overlap == 0 && dom.nblocks() == 1 && !halo.multi_rank()) {
         if (!stream2) {
@@ -5664,11 +5754,13 @@ void Evp::launch_range(int ksub0, int nsub) {
       launch_subcycle_pair(k);
       k += 2;
     } else {
+      to_blocks();
       to_planes();
       launch_subcycle(k);
       k += 1;
     }
   }
+  to_blocks();
   to_planes();   // whoever comes next (finish, download, another range) finds the state where it always was
 }
 
@@ -5699,23 +5791,25 @@ void Evp::subcycles(int ksub0, int nsub, float* elapsed_ms) {
   bool tuning = false;
   if ((can_skew() || can_skew_fold()) && skew_rows_on()) {   // the segment table of the sweep kernel, outside any capture
     const int K = skew_levels(), seg = skew_seg_rows(K);
-    const int tiles_x = skew_strips(K, nullptr), tiles_y = ((dom.ny_block - 2) + seg - 1) / seg;
-    build_skew_rows(K, tiles_x, tiles_y, dom.nblocks(), seg);
+    const int tiles_x = skew_strips(K, nullptr), tiles_y = ((sg().ny - 2) + seg - 1) / seg;
+    build_skew_rows(K, tiles_x, tiles_y, sg().nb, seg);
     if (balance_on() && !(can_skew() && can_trim()) && nsub >= K && !(nsub >= 2 && (can_reside() || can_reside_peer()))) {
       // this loop's sweeps are measured (eagerly: no graph) while a tuning phase lasts; a new phase every bal_every loops
       if (bal_left == 0 && ++bal_since >= bal_every) {
         bal_left = BAL_AGAIN;
         bal_since = 0;
       }
-      const size_t want = 2 * (size_t)(8 * ((std::max(tiles_x * tiles_y * dom.nblocks(), bal_slots) + 7) / 8));
+      const size_t want = 2 * (size_t)(8 * ((std::max(tiles_x * tiles_y * sg().nb, bal_slots) + 7) / 8));
       if (bal_left > 0 && skew_dbg.n < want) skew_dbg.alloc(want);
       tuning = bal_left > 0;
     }
   }
-  if (pairs_ok())
+  if (skew_joined())
+    img_ensure();
+  else if (pairs_ok())
     for (int k = 0; k < 2; ++k)
       if (st2[k].n < 14 * n) st2[k].alloc(14 * n);
-  if ((can_skew() || can_skew_fold()) && !skew_packed) skew_pack();   // (sweeps switched on after prepare(): allocations outside any capture)
+  if ((can_skew() || can_skew_fold()) && (!skew_packed || packed_joined != can_join())) skew_pack();   // (sweeps switched on after prepare(): allocations outside any capture)
   if (can_skew() && can_trim()) build_split(skew_levels());   // (uploads tables: outside any capture)
   if (tuning) graph_ok = false;
   bool replayed = false;

@@ -249,6 +249,9 @@ int cice_evp_finish(cice_ctx *ctx);
  * so the launch geometry -- never a result -- differs from run to run.  0 keeps the static table and replays the graph always),
  * "resident_granules" (one-launch loop on one rank: 0 progress words, 1 data-tagged granules in a free-running loop unless the
  * last step's ice cover left most tiles empty, 2 always),
+ * "skew_join" (0/1, default 1: a one-task domain whose several blocks tile the whole grid -- no eliminated land block, north-south
+ * open or closed -- runs its sweeps on ONE joined image of the blocks, gathered before the first sweep of a range of subcycles
+ * and scattered back behind the last; 0: such domains keep one launch per subcycle),
  * "skew_fill" / "skew_gen_pct" (per cent: static weights of a workgroup's place -- more rows on a CU that holds fewer
  * workgroups, more for the workgroup dispatched first; defaults 26 / 10), "skew_split" (wide-halo slabs: the refresh beside
  * the interior sweep), "skew_subs" (1; 3 wavefronts per level in -DCICE4_AMD_EXPERIMENTS builds).  DESIGN.md sections 3.1, 3.2, 7.
@@ -256,7 +259,7 @@ int cice_evp_finish(cice_ctx *ctx);
  * cice_evp_get_info keys: "derive_metrics" (1 if active), "waves", "rows_per_wave", "fused"
  * (1 if this domain runs two subcycles per launch), "fused_waves", "resident" (1 if the next cice_evp_subcycles
  * of two or more subcycles runs as one launch), "resident_waves", "resident_dense" (1 if with several workgroups per
- * compute unit), "resident_granules" (1 if with the granule hand-off), "resident_map" (the map last chosen, -1 before the first loop), "skew" / "skew_fold" (1 if sweeps apply),
+ * compute unit), "resident_granules" (1 if with the granule hand-off), "resident_map" (the map last chosen, -1 before the first loop), "skew" / "skew_fold" (1 if sweeps apply), "skew_joined" (1 if they run on a joined image of several blocks),
  * "skew_levels", "skew_strips", "skew_seg_rows", "skew_rowact", "skew_balance", "skew_balanced" (sweeps measured so far),
  * "skew_fill", "skew_pairs", "skew_subs", "skew_split", "skew_trim_ext", "last_launches" (kernel launches of the last
  * subcycle range: 1 = the one-launch loop). */
@@ -520,6 +523,14 @@ int cice_transport_remap(cice_ctx *ctx, double dt, const cice_transport_fields *
  * gives up so that every owned column comes out right (checked by a lane-level restatement of the kernel's dependencies),
  * -1 if there is none; *strips = column strips of the block. */
 int cice_debug_skew_layout(int K, int S, int ncol, int cyclic, int *strips);
+/* Test aid, needs no device: the cell map of the image that a ONE-TASK domain of several blocks (cice_domain_create with these
+ * arguments, one task) is joined into for the K-subcycle sweeps (option "skew_join"): an image of (nxg + 2) x (nyg + 2) cells,
+ * row-major, 0-based.  map[cell of the (nblocks, ny_block, nx_block) block arrays] = the image cell that holds the cell's
+ * value: physical cells their own, a ghost cell with a source on the task that of its source, a ghost cell beyond an open or
+ * closed edge its place on the image's outer ring, -1 for the padding of a last block.  Returns the number of block-array
+ * cells (map is filled up to cap entries), 0 if the layout does not qualify (one block; a tripole or cyclic north-south
+ * boundary), -2 for bad arguments. */
+long long cice_debug_join_map(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t *map, long long cap);
 /* Test aid, needs no device: one strip's step of the measured balancing of the sweep's row segments:
  * n tiles with exclusive end rows ends[] (bottom to top, the last one = rows), the workgroups' measured durations[] (any unit),
  * the static weights[] of their places, rows_with_ice[rows] != 0 where a row holds anything to compute (or NULL: every row).
