@@ -886,8 +886,9 @@ int cice_evp_get_info(cice_ctx* ctx, const char* key, int* value) {
   else if (!std::strcmp(key, "fused")) *value = c_->evp->can_fuse() ? 1 : 0;
   else if (!std::strcmp(key, "fused_waves")) *value = c_->evp->fused_waves();
   else if (!std::strcmp(key, "skew")) *value = c_->evp->can_skew() || c_->evp->can_skew_fold() ? 1 : 0;
-  else if (!std::strcmp(key, "skew_fold")) *value = !c_->evp->can_skew() && c_->evp->can_skew_fold() ? 1 : 0;
+  else if (!std::strcmp(key, "skew_fold")) *value = (!c_->evp->can_skew() && c_->evp->can_skew_fold()) || c_->evp->skew_joined_fold() ? 1 : 0;
   else if (!std::strcmp(key, "skew_joined")) *value = c_->evp->skew_joined() ? 1 : 0;
+  else if (!std::strcmp(key, "skew_join_fold")) *value = c_->evp->join_fold_option() ? 1 : 0;
   else if (!std::strcmp(key, "skew_levels")) *value = c_->evp->skew_levels();
   else if (!std::strcmp(key, "skew_subs")) *value = c_->evp->skew_subs(c_->evp->skew_levels());
   else if (!std::strcmp(key, "skew_pairs")) *value = c_->evp->pairs_ok() ? 1 : 0;
@@ -1858,6 +1859,15 @@ int cice_debug_skew_layout(int K, int S, int ncol, int cyclic, int* strips) {
 long long cice_debug_join_map(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t* map, long long cap) {
   try {
     return cice::join_map_debug(nxg, nyg, bsx, bsy, ew, ns, map, cap);
+  } catch (...) {
+    return -2;
+  }
+}
+
+// ... the geometry that admits a tripole fold (option "skew_join_fold"); without a fold the same map
+long long cice_debug_join_map_fold(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t* map, long long cap) {
+  try {
+    return cice::join_map_debug(nxg, nyg, bsx, bsy, ew, ns, map, cap, 1);
   } catch (...) {
     return -2;
   }

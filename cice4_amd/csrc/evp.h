@@ -71,6 +71,8 @@ class Evp {
   bool can_skew() const;     // K subcycles per sweep (k_subcycle_skew) on this domain
   bool can_join() const;     // ... of several blocks: the sweeps run on a joined image of them (join.h)
   bool skew_joined() const { return can_join() && can_skew(); }
+  bool skew_joined_fold() const { return skew_joined() && img.g.fold; }   // ... with a tripole fold carried by a band on the blocks
+  bool join_fold_option() const { return join_fold_on; }
   bool can_split() const;    // ... and the sweep in front of a wide-halo refresh as edge + interior launches
   bool skew_rows_on() const { return (skew_gen_pct > 0 || skew_fill_on() || balance_on()) && skew_seg_opt == 0; }   // segments of unequal length (build_skew_rows)
   bool skew_fill_on() const;
@@ -249,6 +251,12 @@ class Evp {
   void img_ensure();         // allocations and the grid's planes (outside any capture)
   void to_image();
   void to_blocks();
+  // ... under a tripole fold (option "skew_join_fold", off by default): the sweep on the image, the fold carried by a band
+  // of top rows on the blocks beside it
+  bool join_fold_on = false;
+  bool can_join_fold() const;
+  void ensure_join_band(int K);  // the band's buffers and block table (allocations: outside any capture)
+  void launch_subcycle_join_fold(int ksub, int K);
   // in
   DevBuf<double> aice, vice, vsno, aice0, aicen, vicen, strairxT, strairyT, uocn, vocn, ss_tltx,
       ss_tlty;

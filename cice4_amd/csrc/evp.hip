@@ -3062,6 +3062,10 @@ void Evp::set_option(const char* key, int value) {
     join_on = value != 0;
     skew_packed = false;
     skew_rows_key[0] = -1;
+  } else if (!std::strcmp(key, "skew_join_fold")) {   // ... also under a tripole fold (launch_subcycle_join_fold); off by default
+    join_fold_on = value != 0;
+    skew_packed = false;
+    skew_rows_key[0] = -1;
   } else if (!std::strcmp(key, "skew_levels")) {   // 0 = auto
 #ifdef CICE4_AMD_EXPERIMENTS
     CICE_REQUIRE(value == 0 || value == 2 || value == 3 || value == 4 || value == 5 || value == 6 || value == 8,
@@ -3180,6 +3184,10 @@ void Evp::init(const cice_evp_config& c, const cice_evp_grid& g) {
     fwd_is_ew_wrap = ok;
   }
   img.init(dom, stream);   // the blocks as one image for the sweep kernel, where they tile the grid (join.h)
+  {   // ... under a tripole fold only where asked for: option "skew_join_fold", or this variable as the default of a context
+    const char* e = std::getenv("CICE4_AMD_SKEW_JOIN_FOLD");
+    join_fold_on = e && e[0] == '1';
+  }
   // the eight read-only inputs of the momentum equation share one allocation (k_subcycle_skew: one base pointer)
   uarena.alloc(8 * n);
   {
@@ -3781,7 +3789,18 @@ bool Evp::can_skew() const {
 // those keep their paths.
 bool Evp::can_join() const {
   static const bool env_off = [] { const char* e = std::getenv("CICE4_AMD_SKEW_JOIN"); return e && e[0] == '0'; }();
-  return join_on && !env_off && SKEW_WIDE && img.g.ok && fuse_on && !halo.multi_rank() && !halo.has_fold();
+  if (!(join_on && !env_off && SKEW_WIDE && img.g.ok && fuse_on && !halo.multi_rank())) return false;
+  return img.g.fold ? can_join_fold() : !halo.has_fold();
+}
+
+// The same under a tripole fold ("skew_join_fold"; CICE4_AMD_SKEW_JOIN_FOLD=1 makes 1 the default of a context, Evp::init).
+// What the one-block form under a fold asks (can_skew_fold), of the image; and the band -- rows nyg - 2K .. nyg -- has to
+// lie within the top block row, whose blocks then carry it alone.
+bool Evp::can_join_fold() const {
+  if (!join_fold_on || !skew_fold_on || !halo.has_fold() || !halo.fwd_ok() || dom.overlap != 0) return false;
+  if (!img.band_fits(skew_levels())) return false;
+  const long long cells = (long long)(img.g.nx - 2) * (img.g.ny - 2);
+  return cells >= std::max(skew_min_cells, skew_min_cells ? 800000LL : 0LL);
 }
 
 Evp::SweepGeom Evp::sg() const {
@@ -3812,9 +3831,17 @@ void Evp::to_blocks() {
   if (!in_image) return;
   img.split_state(stream, st[cur].p, cur, in_pairs, icetmask.p, iceumask.p);
   ++loop_launches;
+  if (img.g.fold) {
+    // the fold writes u, v of the top physical row and of the ghost row above it whether there is ice or not, and the
+    // ghost row has no copy source: the band of the last sweep holds both rows as the blocks' own path leaves them
+    img.band_top_rows(stream, band[band_k & 1].p, st[cur].p);
+    ++loop_launches;
+  }
   if (img_out) {
     double* const o[9] = {divu.p, rdg_conv.p, rdg_shear.p, shear.p, prs_sig.p, strintx.p, strinty.p, strocnx.p, strocny.p};
-    img.split_out(stream, o, icetmask.p, iceumask.p);
+    // under a fold the band wrote the diagnostics of its rows from nyg - K + 1 up straight into the blocks' arrays:
+    // split_out is restricted to the rows below them (no ordering between the two is needed)
+    img.split_out(stream, o, icetmask.p, iceumask.p, img.g.fold ? img.g.ny - 1 - band_k : -1);
     ++loop_launches;
   }
   in_image = in_pairs = img_out = false;
@@ -4801,6 +4828,92 @@ void Evp::launch_subcycle_skew_fold(int ksub, int K) {
   CICE_HIP(hipGetLastError());
 }
 
+// ---- ... on the joined image of several blocks (join.h) ------------------------------------------------------------------
+// The sweep runs on the image as on an open north boundary; the band stays on the BLOCKS -- k_subcycle on the top block
+// row's blocks, clipped to global rows nyg - 2K .. nyg, and the ordinary halo update of (u, v), which does the ghost copies
+// between blocks and the fold: the form of the per-subcycle path on these blocks, which is pinned to the reference.  Two
+// small kernels (join.hip) carry rows nyg - 2K - 1 .. nyg + 1 of the image into the band before the sweep and rows
+// nyg - K + 1 .. nyg + 1 of the band into the image after it.  The stale-row argument above holds unchanged.
+void Evp::ensure_join_band(int K) {
+  for (int k = 0; k < 2; ++k)
+    if (band[k].n < 14 * n) {
+      band[k].alloc(14 * n);
+      band[k].zero(stream);      // (padding of last blocks is never gathered: the kernels may load it)
+    }
+  if (blk_band.n != 6 * (size_t)dom.nblocks() || band_k != K) {
+    std::vector<int32_t> hb;
+    for (int gid : dom.local) {
+      const Block& b = dom.all[gid];
+      // blocks below the top block row: an empty range of rows
+      const int jlo = b.jb == dom.nby - 1 ? b.jhi - 2 * K : b.jhi + 3;
+      hb.insert(hb.end(), {b.ilo, b.ihi, jlo, b.jhi, 0, 0});
+    }
+    blk_band.alloc(hb.size());
+    blk_band.upload(hb.data(), stream);
+    band_k = K;
+  }
+  CICE_HIP(hipStreamSynchronize(stream));
+  if (!stream2) CICE_HIP(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));   // (outside any capture)
+  if (!ev_fork) CICE_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+  if (!ev_join) CICE_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+}
+
+void Evp::launch_subcycle_join_fold(int ksub, int K) {
+  CICE_REQUIRE(in_image && img.g.fold && band[0].n >= 14 * n && band_k == K && blk_band.n == 6 * (size_t)dom.nblocks(),
+               "sweep on the image with a fold: the band has not been set up");
+  const int jhi = img.g.top_jhi, jb = jhi - 2 * K, jm = jhi - K + 1;   // local rows of the top block row: first of the band, first taken from it
+  // 1. the band's two copies start as the state of global rows nyg-2K-1 .. nyg+1, ghost cells of the blocks included
+  img.band_gather(stream, K, cur, in_pairs, band[0].p, band[1].p);
+  // 2. the sweep on the image (it flips `cur` and, as the last of evp(dt), leaves planes and the diagnostics in img.out)
+  static const bool beside = [] { const char* e = std::getenv("CICE4_AMD_SKEW_FOLD_BESIDE"); return !(e && e[0] == '0'); }();
+  if (beside) {
+    CICE_HIP(hipEventRecord(ev_fork, stream));
+    CICE_HIP(hipStreamWaitEvent(stream2, ev_fork, 0));
+    launch_subcycle_skew(ksub, K, /*flip_and_halo=*/false, stream2);
+    CICE_HIP(hipEventRecord(ev_join, stream2));
+  } else {
+    launch_subcycle_skew(ksub, K, /*flip_and_halo=*/false);
+  }
+  // 3. the band, one subcycle at a time, on the blocks of the top block row.  The last subcycle of evp(dt) writes the
+  //    diagnostics of rows jm .. jhi+1 into the blocks' arrays; the sweep's go to img.out, and split_out leaves those rows alone.
+  for (int s = 0; s < K; ++s) {
+    SubArgs a = make_args();
+    double* in = band[s & 1].p;
+    double* out = band[(s + 1) & 1].p;
+    a.u_in = in; a.v_in = in + n; a.sig_in = in + 2 * n;
+    a.u_out = out; a.v_out = out + n; a.sig_out = out + 2 * n;
+    for (int c = 0; c < 12; ++c) {
+      a.sig_in_p[c] = a.sig_in + (size_t)c * n;
+      a.sig_out_p[c] = a.sig_out + (size_t)c * n;
+    }
+    a.blk = blk_band.p;
+    a.diag_jmin = jm;
+    const int trows = waves * rows_per_wave;
+    a.tiles_x = ((dom.nx_block - 2) + (TX - 1) - 1) / (TX - 1);
+    a.tiles_y = ((jhi - jb + 1) + (trows - 1) - 1) / (trows - 1);
+    const int nt = a.tiles_x * a.tiles_y * a.nblocks;
+    const dim3 g(8 * ((nt + 7) / 8));
+    const bool last = (ksub + s == sc.ndte), damp = sc.evp_damping != 0;
+    switch (waves * 100 + rows_per_wave) {
+      case 801: launch_wr<8, 1>(a, last, damp, g, stream); break;
+      case 802: launch_wr<8, 2>(a, last, damp, g, stream); break;
+      case 804: launch_wr<8, 4>(a, last, damp, g, stream); break;
+      case 401: launch_wr<4, 1>(a, last, damp, g, stream); break;
+      case 402: launch_wr<4, 2>(a, last, damp, g, stream); break;
+      case 404: launch_wr<4, 4>(a, last, damp, g, stream); break;
+      case 408: launch_wr<4, 8>(a, last, damp, g, stream); break;
+      case 1601: launch_wr<16, 1>(a, last, damp, g, stream); break;
+      case 1602: launch_wr<16, 2>(a, last, damp, g, stream); break;
+      default: throw Error{CICE_EINVAL, "unsupported (waves, rows_per_wave) combination"};
+    }
+    halo.update_r8(out, 2, n, /*wrap=*/false, LOC_NECORNER, KIND_VECTOR);   // ghost copies between blocks and the fold (:397-402)
+  }
+  // 4. global rows nyg-K+1 .. nyg+1 of the band replace the sweep's in the copy it wrote
+  if (beside) CICE_HIP(hipStreamWaitEvent(stream, ev_join, 0));
+  img.band_scatter(stream, K, cur, in_pairs, band[K & 1].p);
+  CICE_HIP(hipGetLastError());
+}
+
 // ---- resident loop ------------------------------------------------------------------------------------------------
 // One block on this rank, nothing to exchange with other ranks or across a tripole fold during the subcycling, on-rank
 // ghosts served by forwarding, and at most one tile per CU (the hand-off form used is the one measured for one
@@ -5742,6 +5855,8 @@ void Evp::launch_range(int ksub0, int nsub) {
         const int ext = std::min(dom.overlap, next - kend);
         if (ext == 0 && split) launch_subcycle_skew_split(k, K);   // a refresh follows: edge segments first
         else launch_subcycle_skew_ext(k, K, ext);
+      } else if (joined && img.g.fold) {
+        launch_subcycle_join_fold(k, K);
       } else {
         launch_subcycle_skew(k, K);
       }
@@ -5788,6 +5903,7 @@ void Evp::subcycles(int ksub0, int nsub, float* elapsed_ms) {
   static const bool env_comm_graph = std::getenv("CICE4_AMD_COMM_GRAPH") != nullptr;
   bool graph_ok = use_graph && nsub > 1 && (!halo.multi_rank() || comm_graph || env_comm_graph);
   if (!can_skew() && can_skew_fold()) ensure_band(skew_levels());
+  if (skew_joined_fold()) ensure_join_band(skew_levels());
   bool tuning = false;
   if ((can_skew() || can_skew_fold()) && skew_rows_on()) {   // the segment table of the sweep kernel, outside any capture
     const int K = skew_levels(), seg = skew_seg_rows(K);

@@ -7,11 +7,12 @@
 namespace cice {
 
 // ---- geometry (host, no device) ----------------------------------------------------------------------------------------
-bool join_geometry(const Domain& d, JoinGeom& g) {
+bool join_geometry(const Domain& d, JoinGeom& g, bool allow_fold) {
   g = JoinGeom{};
   const int nb = d.nblocks();
   if (d.nranks != 1 || d.overlap != 0 || d.self_comm || !d.rsrc.empty() || !d.hfill.empty()) return false;
-  if (d.tripole() || d.ns == BND_CYCLIC) return false;     // (a fold over several blocks: the blocks keep their own path)
+  if ((d.tripole() && !allow_fold) || d.ns == BND_CYCLIC) return false;   // (a fold over several blocks: only where asked for)
+  if (d.tripole() && d.ew != BND_CYCLIC) return false;
   if (d.ew != BND_OPEN && d.ew != BND_CYCLIC && d.ew != BND_CLOSED) return false;
   if (nb < 2 || nb != d.nbx * d.nby || (int)d.all.size() != nb) return false;   // one block: nothing to join
   for (const Block& b : d.all)
@@ -46,9 +47,28 @@ bool join_geometry(const Domain& d, JoinGeom& g) {
         if (i >= b.ilo && j >= b.jlo) g.tnat[c] = nat(b, i, j);
       }
   }
+  // Under a fold the top ghost row of the top block row is written by the fold, from no copy source: its cells keep the
+  // place on the image's top ring they were given above.  A copy into one of them would alias it to a physical cell.
+  std::vector<char> fold_row;
+  if (d.tripole()) {
+    fold_row.assign(g.nblk, 0);
+    const Block& t0 = d.all[(size_t)(d.nby - 1) * d.nbx];
+    for (int ib = 0; ib < d.nbx; ++ib) {
+      const Block& b = d.all[(size_t)(d.nby - 1) * d.nbx + ib];
+      if (b.jlo != t0.jlo || b.jhi != t0.jhi || b.local_id != t0.local_id + ib) return false;
+      for (int i = 1; i <= d.nx_block; ++i) fold_row[addr(b, i, b.jhi + 1)] = 1;
+    }
+    g.fold = true;
+    g.nxb = d.nx_block;
+    g.nyb = d.ny_block;
+    g.top_nb = d.nbx;
+    g.top_jhi = t0.jhi;
+    g.top_first = (size_t)t0.local_id * np;
+  }
   for (size_t e = 0; e < d.hsrc.size(); ++e) {
     const size_t s = (size_t)d.hsrc[e], c = (size_t)d.hdst[e];
     if (s >= g.nblk || c >= g.nblk || g.usrc[s] != (int32_t)s) return false;   // (sources are physical cells)
+    if (g.fold && fold_row[c]) return false;
     g.map[c] = g.map[s];
     g.usrc[c] = (int32_t)s;
   }
@@ -68,13 +88,13 @@ bool join_geometry(const Domain& d, JoinGeom& g) {
   return true;
 }
 
-long long join_map_debug(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t* map, long long cap) {
+long long join_map_debug(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t* map, long long cap, int fold) {
   if (nxg < 1 || nyg < 1 || bsx < 1 || bsy < 1 || cap < 0 || (cap > 0 && !map)) return -2;
   Domain d;
   const char* msg = d.create(nxg, nyg, bsx, bsy, ew, ns, 0, 1, 1);
   if (msg && msg[0]) return -2;
   JoinGeom g;
-  if (!join_geometry(d, g)) return 0;
+  if (!join_geometry(d, g, fold != 0)) return 0;
   for (long long c = 0; c < std::min<long long>(cap, (long long)g.nblk); ++c) map[c] = g.map[(size_t)c];
   return (long long)g.nblk;
 }
@@ -194,19 +214,84 @@ struct OutPtrs { double* p[9]; };
 __global__ __launch_bounds__(256) void k_split_out(size_t nb, size_t ni, const int32_t* __restrict__ tnat,
                                                    const int32_t* __restrict__ umap, const int32_t* __restrict__ usrc,
                                                    const int32_t* __restrict__ tmk, const int32_t* __restrict__ umk,
-                                                   const double* __restrict__ in, const OutPtrs o) {
+                                                   const double* __restrict__ in, const OutPtrs o, int32_t q_end) {
   const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nb) return;
   const int32_t t0 = tnat[c];
-  if (t0 >= 0 && tmk[c] == 1) {
+  if (t0 >= 0 && t0 < q_end && tmk[c] == 1) {
 #pragma unroll
     for (int p = 0; p < 5; ++p) o.p[p][c] = in[(size_t)p * ni + (size_t)t0];
   }
-  if (usrc[c] == (int32_t)c && umk[c] != 0) {
+  if (usrc[c] == (int32_t)c && umk[c] != 0 && umap[c] < q_end) {
     const size_t q = (size_t)umap[c];
 #pragma unroll
     for (int p = 5; p < 9; ++p) o.p[p][c] = in[(size_t)p * ni + q];
   }
+}
+
+// ---- the band of top rows under a fold: block geometry <-> image ----
+// The rows of the top block row's blocks from local row j0 (0-based) on, `rows` of them, every column: from the image
+// (through map: a ghost cell reads its source's image cell, the top ghost row its place on the ring) into both band copies.
+template <bool PAIRS>
+__global__ __launch_bounds__(256) void k_band_from_image(size_t cells, int nxb, int rows, int j0, size_t first, size_t np, size_t nb,
+                                                         size_t ni, const int32_t* __restrict__ map,
+                                                         const double* __restrict__ in, double* __restrict__ out0,
+                                                         double* __restrict__ out1) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cells) return;
+  const size_t per = (size_t)rows * nxb, b = t / per, rem = t - b * per;
+  const size_t c = first + b * np + (size_t)j0 * nxb + rem;
+  const int32_t m = map[c];
+  if (m < 0) return;                     // padding of a last block
+  const size_t q = (size_t)m;
+#pragma unroll
+  for (int p = 0; p < 7; ++p) {
+    jdbl2 v;
+    if (PAIRS) {
+      v = *(const jdbl2*)(in + 2 * ((size_t)p * ni + q));
+    } else {
+      v.x = in[(size_t)(2 * p) * ni + q];
+      v.y = in[(size_t)(2 * p + 1) * ni + q];
+    }
+    out0[(size_t)(2 * p) * nb + c] = v.x;
+    out0[(size_t)(2 * p + 1) * nb + c] = v.y;
+    out1[(size_t)(2 * p) * nb + c] = v.x;
+    out1[(size_t)(2 * p + 1) * nb + c] = v.y;
+  }
+}
+
+// `cells` cells of the image from cell q0 on (whole rows, ring included) take the band's values
+template <bool PAIRS>
+__global__ __launch_bounds__(256) void k_band_to_image(size_t cells, size_t q0, size_t nb, size_t ni, const int32_t* __restrict__ inv,
+                                                       const double* __restrict__ in, double* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cells) return;
+  const size_t q = q0 + t, s = (size_t)inv[q];
+#pragma unroll
+  for (int p = 0; p < 7; ++p) {
+    jdbl2 v;
+    v.x = in[(size_t)(2 * p) * nb + s];
+    v.y = in[(size_t)(2 * p + 1) * nb + s];
+    if (PAIRS) {
+      *(jdbl2*)(out + 2 * ((size_t)p * ni + q)) = v;
+    } else {
+      out[(size_t)(2 * p) * ni + q] = v.x;
+      out[(size_t)(2 * p + 1) * ni + q] = v.y;
+    }
+  }
+}
+
+// u | v of two rows of the top block row's blocks (the top physical row and the ghost row above it), every mapped column
+__global__ __launch_bounds__(256) void k_band_top_rows(size_t cells, int nxb, int j0, size_t first, size_t np, size_t nb,
+                                                       const int32_t* __restrict__ map, const double* __restrict__ in,
+                                                       double* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cells) return;
+  const size_t per = (size_t)2 * nxb, b = t / per, rem = t - b * per;
+  const size_t c = first + b * np + (size_t)j0 * nxb + rem;
+  if (map[c] < 0) return;
+  out[c] = in[c];
+  out[nb + c] = in[nb + c];
 }
 
 inline dim3 grid_of(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
@@ -216,7 +301,7 @@ inline dim3 grid_of(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 // ---- device side --------------------------------------------------------------------------------------------------------
 void JoinImage::init(const Domain& d, hipStream_t s) {
   grid_done = false;
-  if (!join_geometry(d, g)) return;
+  if (!join_geometry(d, g, /*allow_fold=*/true)) return;   // (whether a fold is swept on the image: Evp::can_join)
   inv.alloc(g.n);
   inv.upload(g.inv.data(), s);
   tnat.alloc(g.nblk);
@@ -275,11 +360,40 @@ void JoinImage::split_state(hipStream_t s, double* st_b, int cur, bool pairs, co
                        (const int32_t*)umap.p, (const int32_t*)usrc.p, tmk_b, umk_b, (const double*)st[cur].p, st_b);
 }
 
-void JoinImage::split_out(hipStream_t s, double* const out_b[9], const int32_t* tmk_b, const int32_t* umk_b) {
+void JoinImage::split_out(hipStream_t s, double* const out_b[9], const int32_t* tmk_b, const int32_t* umk_b, int row_end) {
+  const int32_t q_end = row_end < 0 || row_end > g.ny ? (int32_t)g.n : (int32_t)((size_t)row_end * g.nx);
   OutPtrs o;
   for (int p = 0; p < 9; ++p) o.p[p] = out_b[p];
   hipLaunchKernelGGL(k_split_out, grid_of(g.nblk), dim3(256), 0, s, g.nblk, g.n, (const int32_t*)tnat.p, (const int32_t*)umap.p,
-                     (const int32_t*)usrc.p, tmk_b, umk_b, (const double*)out.p, o);
+                     (const int32_t*)usrc.p, tmk_b, umk_b, (const double*)out.p, o, q_end);
+}
+
+// (the image's row of global row r, 1-based, is r; a block's 0-based row of its local row j is j - 1)
+void JoinImage::band_gather(hipStream_t s, int K, int cur, bool pairs, double* band0, double* band1) {
+  const int rows = 2 * K + 3, j0 = g.top_jhi - 2 * K - 2;   // local rows jhi-2K-1 .. jhi+1
+  const size_t cells = (size_t)g.top_nb * rows * g.nxb, np = (size_t)g.nxb * g.nyb;
+  if (pairs)
+    hipLaunchKernelGGL(k_band_from_image<true>, grid_of(cells), dim3(256), 0, s, cells, g.nxb, rows, j0, g.top_first, np, g.nblk, g.n,
+                       (const int32_t*)umap.p, (const double*)st[cur].p, band0, band1);
+  else
+    hipLaunchKernelGGL(k_band_from_image<false>, grid_of(cells), dim3(256), 0, s, cells, g.nxb, rows, j0, g.top_first, np, g.nblk, g.n,
+                       (const int32_t*)umap.p, (const double*)st[cur].p, band0, band1);
+}
+
+void JoinImage::band_scatter(hipStream_t s, int K, int cur, bool pairs, const double* band) {
+  const size_t cells = (size_t)(K + 1) * g.nx, q0 = (size_t)(g.ny - 1 - K) * g.nx;   // image rows nyg-K+1 .. nyg+1
+  if (pairs)
+    hipLaunchKernelGGL(k_band_to_image<true>, grid_of(cells), dim3(256), 0, s, cells, q0, g.nblk, g.n, (const int32_t*)inv.p, band,
+                       st[cur].p);
+  else
+    hipLaunchKernelGGL(k_band_to_image<false>, grid_of(cells), dim3(256), 0, s, cells, q0, g.nblk, g.n, (const int32_t*)inv.p, band,
+                       st[cur].p);
+}
+
+void JoinImage::band_top_rows(hipStream_t s, const double* band, double* st_b) {
+  const size_t cells = (size_t)g.top_nb * 2 * g.nxb, np = (size_t)g.nxb * g.nyb;
+  hipLaunchKernelGGL(k_band_top_rows, grid_of(cells), dim3(256), 0, s, cells, g.nxb, g.top_jhi - 1, g.top_first, np, g.nblk,
+                     (const int32_t*)umap.p, band, st_b);
 }
 
 }  // namespace cice

@@ -118,20 +118,22 @@ def load(flavour="standalone"):
     return _libs[flavour]
 
 
-def join_map(nxg, nyg, bsx, bsy, ew=1, ns=0, flavour="standalone"):
+def join_map(nxg, nyg, bsx, bsy, ew=1, ns=0, flavour="standalone", fold=False):
     """cice_debug_join_map (no device): the cell map of the image that a one-task domain in blocks of bsx x bsy is joined
     into for the K-subcycle sweeps (option "skew_join"), as an int32 array (nblocks, bsy + 2, bsx + 2) of 0-based cells of the
-    row-major (nyg + 2) x (nxg + 2) image, -1 for padding; None if the layout does not qualify."""
+    row-major (nyg + 2) x (nxg + 2) image, -1 for padding; None if the layout does not qualify.  fold=True: the geometry of
+    option "skew_join_fold", which admits a tripole north boundary (cice_debug_join_map_fold)."""
     L = load(flavour)
-    L.cice_debug_join_map.restype = C.c_longlong
-    L.cice_debug_join_map.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_longlong]
-    n = L.cice_debug_join_map(nxg, nyg, bsx, bsy, ew, ns, None, 0)
+    fn = L.cice_debug_join_map_fold if fold else L.cice_debug_join_map
+    fn.restype = C.c_longlong
+    fn.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_longlong]
+    n = fn(nxg, nyg, bsx, bsy, ew, ns, None, 0)
     if n < 0:
         raise CiceError(f"cice_debug_join_map: bad arguments ({n})")
     if n == 0:
         return None
     m = np.full(n, -2, np.int32)
-    assert L.cice_debug_join_map(nxg, nyg, bsx, bsy, ew, ns, _i4(m), n) == n
+    assert fn(nxg, nyg, bsx, bsy, ew, ns, _i4(m), n) == n
     return m.reshape(-1, bsy + 2, bsx + 2)
 
 

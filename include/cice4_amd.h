@@ -252,6 +252,10 @@ int cice_evp_finish(cice_ctx *ctx);
  * "skew_join" (0/1, default 1: a one-task domain whose several blocks tile the whole grid -- no eliminated land block, north-south
  * open or closed -- runs its sweeps on ONE joined image of the blocks, gathered before the first sweep of a range of subcycles
  * and scattered back behind the last; 0: such domains keep one launch per subcycle),
+ * "skew_join_fold" (0/1, default 0, or 1 where the environment has CICE4_AMD_SKEW_JOIN_FOLD=1: the same under a 'tripole' /
+ * 'tripoleT' north boundary -- the sweep on the image as on an open boundary, the fold carried by a band of the top 2K + 1 rows
+ * that runs one subcycle at a time on the blocks of the top block row, which has to hold those rows; needs "skew_fold" and
+ * "skew_join"; 0: such domains keep one launch per subcycle plus the halo update with the fold),
  * "skew_fill" / "skew_gen_pct" (per cent: static weights of a workgroup's place -- more rows on a CU that holds fewer
  * workgroups, more for the workgroup dispatched first; defaults 26 / 10), "skew_split" (wide-halo slabs: the refresh beside
  * the interior sweep), "skew_subs" (1; 3 wavefronts per level in -DCICE4_AMD_EXPERIMENTS builds).  DESIGN.md sections 3.1, 3.2, 7.
@@ -259,7 +263,7 @@ int cice_evp_finish(cice_ctx *ctx);
  * cice_evp_get_info keys: "derive_metrics" (1 if active), "waves", "rows_per_wave", "fused"
  * (1 if this domain runs two subcycles per launch), "fused_waves", "resident" (1 if the next cice_evp_subcycles
  * of two or more subcycles runs as one launch), "resident_waves", "resident_dense" (1 if with several workgroups per
- * compute unit), "resident_granules" (1 if with the granule hand-off), "resident_map" (the map last chosen, -1 before the first loop), "skew" / "skew_fold" (1 if sweeps apply), "skew_joined" (1 if they run on a joined image of several blocks),
+ * compute unit), "resident_granules" (1 if with the granule hand-off), "resident_map" (the map last chosen, -1 before the first loop), "skew" / "skew_fold" (1 if sweeps apply), "skew_joined" (1 if they run on a joined image of several blocks; with "skew_fold" also 1: under a tripole fold), "skew_join_fold" (the option read back),
  * "skew_levels", "skew_strips", "skew_seg_rows", "skew_rowact", "skew_balance", "skew_balanced" (sweeps measured so far),
  * "skew_fill", "skew_pairs", "skew_subs", "skew_split", "skew_trim_ext", "last_launches" (kernel launches of the last
  * subcycle range: 1 = the one-launch loop). */
@@ -531,6 +535,9 @@ int cice_debug_skew_layout(int K, int S, int ncol, int cyclic, int *strips);
  * cells (map is filled up to cap entries), 0 if the layout does not qualify (one block; a tripole or cyclic north-south
  * boundary), -2 for bad arguments. */
 long long cice_debug_join_map(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t *map, long long cap);
+/* The same for the geometry that admits a tripole fold (option "skew_join_fold"): ns = 3 / 4 qualify as well; the top ghost row
+ * of the top block row, which the fold writes, maps to its own place on the image's top ring.  Without a fold: the same map. */
+long long cice_debug_join_map_fold(int nxg, int nyg, int bsx, int bsy, int ew, int ns, int32_t *map, long long cap);
 /* Test aid, needs no device: one strip's step of the measured balancing of the sweep's row segments:
  * n tiles with exclusive end rows ends[] (bottom to top, the last one = rows), the workgroups' measured durations[] (any unit),
  * the static weights[] of their places, rows_with_ice[rows] != 0 where a row holds anything to compute (or NULL: every row).
