@@ -171,12 +171,18 @@ struct cice_ctx {
 
 static std::string g_create_err;
 
-#define CICE_TRY(ctx_) \
+#define CICE_TRY_QUEUED(ctx_) \
   cice_ctx* c_ = (ctx_); \
   if (!c_) return CICE_EINVAL; \
   try {                        \
     c_->bind_device();         \
     c_->fan.forked = false;   /* an entry that failed between fork and join leaves nothing behind for the next */
+// Every entry but the two that may leave one-launch EVP loops pending (cice_evp_subcycles, and cice_evp_get_info asked for
+// "resident_pending") first looks at the records of the pending ones (Evp::retire_resident): whatever it reads, launches or
+// changes then finds the state a wait behind every loop would have left.
+#define CICE_TRY(ctx_)  \
+  CICE_TRY_QUEUED(ctx_) \
+    if (c_->evp) c_->evp->retire_resident();
 #define CICE_CATCH                                            \
   }                                                           \
   catch (const Error& e) {                                    \
@@ -867,7 +873,7 @@ int cice_evp_pin_fields(cice_ctx* ctx, const cice_evp_fields* f) {
 }
 int cice_evp_prepare(cice_ctx* ctx, double dt) { CICE_TRY(ctx) c_->chain_ready = false; NEED_EVP; c_->evp->forget_host_state(); c_->evp->prepare(dt); CICE_CATCH }
 int cice_evp_subcycles(cice_ctx* ctx, int ksub0, int nsub, float* ms) {
-  CICE_TRY(ctx) c_->chain_ready = false; NEED_EVP; c_->evp->forget_host_state(); c_->evp->subcycles(ksub0, nsub, ms); CICE_CATCH
+  CICE_TRY_QUEUED(ctx) c_->chain_ready = false; NEED_EVP; c_->evp->forget_host_state(); c_->evp->subcycles(ksub0, nsub, ms); CICE_CATCH
 }
 int cice_evp_finish(cice_ctx* ctx) { CICE_TRY(ctx) c_->chain_ready = false; NEED_EVP; c_->evp->forget_host_state(); c_->evp->finish(); CICE_CATCH }
 int cice_evp_download_stresses(cice_ctx* ctx, cice_evp_fields* f) {
@@ -877,9 +883,14 @@ int cice_evp_set_option(cice_ctx* ctx, const char* key, int value) {
   CICE_TRY(ctx) NEED_EVP; CICE_REQUIRE(key, "NULL key"); c_->evp->set_option(key, value); CICE_CATCH
 }
 int cice_evp_get_info(cice_ctx* ctx, const char* key, int* value) {
-  CICE_TRY(ctx)
+  CICE_TRY_QUEUED(ctx)
   NEED_EVP;
   CICE_REQUIRE(key && value, "NULL argument");
+  if (!std::strcmp(key, "resident_pending")) {   // one-launch loops queued whose outcome nobody has looked at yet
+    *value = c_->evp->resident_pending();
+    return CICE_OK;
+  }
+  c_->evp->retire_resident();   // (every other key describes the object as a wait behind every loop would have left it)
   if (!std::strcmp(key, "derive_metrics")) *value = c_->evp->derives_metrics() ? 1 : 0;
   else if (!std::strcmp(key, "waves")) *value = c_->evp->tile_waves();
   else if (!std::strcmp(key, "rows_per_wave")) *value = c_->evp->tile_rows();
@@ -1844,6 +1855,16 @@ int cice_transport_remap(cice_ctx* ctx, double dt, const cice_transport_fields* 
 
 // test aid, no device needed: smallest shift of the sweep kernel's strip layout that is right for a block of ncol columns
 // (K levels, S wavefronts per level), -1 if none; *strips = column strips of the block with it
+// host only (tests): what the retire of n pending one-launch loops does -- see evp_resident_plan
+int cice_debug_resident_plan(int n, const uint32_t* word0, const int32_t* cur, const int32_t* flips, const int32_t* ident,
+                             int cur_now, int flips_now, int ident_now, int32_t out[5]) {
+  if (n < 0 || !out || (n > 0 && (!word0 || !cur || !flips || !ident))) return CICE_EINVAL;
+  int o[5];
+  evp_resident_plan(n, word0, cur, flips, ident, cur_now, flips_now, ident_now, o);
+  for (int k = 0; k < 5; ++k) out[k] = o[k];
+  return CICE_OK;
+}
+
 int cice_debug_skew_layout(int K, int S, int ncol, int cyclic, int* strips) {
   if (K < 2 || K > 8 || (S != 1 && S != 3) || ncol < 1) return -2;
   for (int shift = 0; shift < 2 * K + 4; ++shift)

@@ -65,6 +65,14 @@ class Evp {
   const double* d_aicen() const { return aicen.p; }
   const double* d_vicen() const { return vicen.p; }
   int last_launches = 0;     // subcycle-loop kernel launches of the last subcycles() call (1: the one-launch loop)
+  // One-launch loops of a one-rank domain are queued back to back: an untimed subcycles() that takes the loop returns once
+  // the launch and the read-back of its abort record are in the stream, and the records are looked at later, in order
+  // (run_resident).  retire_resident() waits for the stream and leaves the object as the synchronous code would have left
+  // it -- a loop that gave up, and every range queued behind it, is run again; every other entry calls it first.
+  static constexpr int RES_RING = 16;   // launches in flight at most: what a late time-out costs to run again (16 ranges
+                                        // of ~1 ms), and what one drain of the queue per RES_RING calls costs (1/16 of the gap)
+  void retire_resident();
+  int resident_pending() const { return (int)res_pending.size(); }
   bool peer_buffers_fine() const { return res_xu[0].fine && res_xu[1].fine && res_rprog.fine; }   // what other devices write / poll is fine-grained memory
   bool resident_dense() const; // three 4-wavefront workgroups per CU instead of one workgroup per CU
   bool granules_in_use() const { return can_reside() && !halo.multi_rank() && granules_on() && !resident_dense(); }   // the one-launch loop hands its edge velocities on as data-tagged granules
@@ -182,7 +190,17 @@ class Evp {
   int res_retry_in = 0;          // calls left until then (0: nothing to forgive, or not forgivable)
   int res_occ[5][2][6] = {};     // workgroups of k_evp_resident<W, DAMP, PEER | FOLD | GRAN> one CU holds (last index: plain, PEER, FOLD, GRAN, FOLD + GRAN, PEER + FOLD), 0 = not asked yet
   int res_gran = 1;              // one-rank domains without a fold: edge velocities travel as data-tagged granules (option "resident_granules": 0 never, 1 by the ice cover, 2 always)
-  unsigned* res_why = nullptr;   // page-locked: the eight words read back behind every one-launch loop
+  unsigned* res_why = nullptr;   // page-locked [RES_RING + 1][8]: the eight words read back behind every one-launch loop (last slot: the synchronous path)
+  struct ResPending { int ksub0, nsub, cur, flips; bool copies_identical, dense, map; unsigned epoch0; int slot; };
+  std::vector<ResPending> res_pending;   // launches whose record nobody has looked at yet, oldest first
+  bool res_async = true;         // option "resident_async" / CICE4_AMD_RESIDENT_ASYNC=0: 0 waits for every launch as before
+  bool res_defer = false;        // this subcycles() call may leave its launch pending
+  int res_ncu = 0;               // compute units of the device (0: not asked yet)
+  int device_cus();
+  bool resident_tables_current() const;
+  void resident_cover(unsigned word7, bool map);                    // res_sparse from the ice cover k_res_choose_map counted
+  void resident_gave_up(const unsigned* why, bool dense, bool peer);   // message, fall-back state, words and granules zeroed
+  void run_range(int ksub0, int nsub, float* elapsed_ms, bool try_resident);
   bool res_sparse = false;       // the last step's ice cover left most tiles of the loop empty (run_resident reads k_res_choose_map's count)
   bool granules_on() const;
   DevBuf<int32_t> res_src;       // [cells] the owned U-cell whose velocity a cell holds, -1: nobody's
@@ -300,6 +318,10 @@ class Evp {
   SubArgs make_args() const;
   void drop_graph();
 };
+
+// host-only: the bookkeeping of Evp::retire_resident on a sequence of pending records (evp.hip)
+void evp_resident_plan(int n, const unsigned* word0, const int* cur, const int* flips, const int* ident, int cur_now, int flips_now,
+                       int ident_now, int out[5]);
 
 // host-only: is the sweep kernel's column layout right for a ring of ncol + 1 positions with this shift? (evp.hip: skew_layout_ok)
 bool evp_skew_layout_ok(int K, int S, int ncol, int shift, bool cyc);

@@ -2983,6 +2983,10 @@ inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // ---------------------------------------------------------------------------------------------
 Evp::~Evp() {
+  if (!res_pending.empty()) {   // nobody can read the results any more: wait for the launches, run nothing again
+    (void)hipStreamSynchronize(stream);
+    res_pending.clear();
+  }
   drop_graph();
   if (res_done_ev) (void)hipEventDestroy(res_done_ev);
   for (hipEvent_t e : {res_t0, res_t1, sub_t0, sub_t1})
@@ -3000,7 +3004,9 @@ void Evp::drop_graph() {
 }
 
 void Evp::set_option(const char* key, int value) {
-  if (!std::strcmp(key, "waves")) {
+  if (!std::strcmp(key, "resident_async")) {       // 0: wait for every one-launch loop before the call returns (A/B runs)
+    res_async = value != 0;
+  } else if (!std::strcmp(key, "waves")) {
     CICE_REQUIRE(value == 4 || value == 8 || value == 16, "waves must be 4, 8 or 16");
     waves = value;
   } else if (!std::strcmp(key, "rows_per_wave")) {
@@ -5593,7 +5599,126 @@ int Evp::resident_occupancy(int W, bool damp, bool peer) {
   return c > 0 ? c : 0;
 }
 
-// subcycles ksub0 .. ksub0+nsub-1 in one launch; false: not done (time-out), the state is as it was
+// compute units of the device this object lives on (asked once: the answer costs two runtime calls)
+int Evp::device_cus() {
+  if (res_ncu == 0) {
+    int dev = 0, v = 0;
+    res_ncu = 256;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      res_ncu = v;
+  }
+  return res_ncu;
+}
+
+// the tables of the one-rank loop are those the next launch would use (nothing is built or uploaded under pending launches)
+bool Evp::resident_tables_current() const { return res_deps.n != 0 && !res_peer_built && resident_waves() == res_w; }
+
+// Which shape the NEXT call takes (granules_on): under an ice cover that leaves most tiles empty three barrier-coupled
+// workgroups per CU win -- a CU then holds one tile with ice and two without (gx1 size, polar caps: 231 k subcycles/s
+// against 205 k for the granule loop; fully covered 186 k against 200 k).  The cover of one step is the cover of the
+// next to within a few cells; hysteresis keeps the tables from being rebuilt back and forth.
+void Evp::resident_cover(unsigned word7, bool map) {
+  const int cover[3] = {0, (int)(word7 >> 16), (int)(word7 & 0xffffu)};
+  if (map && cover[2] > 0) {
+    const int pct = (int)(100LL * cover[1] / cover[2]);
+    if (pct < 50) res_sparse = true;
+    else if (pct > 60) res_sparse = false;
+  }
+}
+
+// a launch gave up (why: its eight words): say so, choose what later calls run, leave words and granules as a first launch finds them
+void Evp::resident_gave_up(const unsigned* why, bool dense, bool peer) {
+  if (why[1]) {   // this rank's own first time-out (none: the word came from another rank)
+    std::fprintf(stderr, "cice4_amd: rank %d: tile %u of %d gave up %s (subcycle %u of the launch, word wanted %u), producers "
+                         "not heard from: lanes %08x%08x of its dependency list:", dom.rank, why[2], res_tiles,
+                 why[1] == 1 ? "waiting for the neighbouring ranks' loops to begin" : why[1] == 4 ? "polling the granules of its halo" : "waiting for the producers of its halo",
+                 why[3], why[6], why[5], why[4]);
+    std::vector<int32_t> dl(RES_MAXDEP);
+    CICE_HIP(hipMemcpy(dl.data(), res_deps.p + (size_t)why[2] * RES_MAXDEP, RES_MAXDEP * 4, hipMemcpyDeviceToHost));
+    const unsigned long long ms = ((unsigned long long)why[5] << 32) | why[4];
+    for (int l = 0; l < RES_MAXDEP; ++l)
+      if ((ms >> l) & 1) {
+        unsigned seen = 0;
+        const int d = dl[l];
+        const unsigned* wp = d <= -2 ? res_rprog.p + (size_t)(-2 - d) * RES_STRIDE : res_prog.p + (size_t)d * RES_STRIDE;
+        CICE_HIP(hipMemcpy(&seen, wp, 4, hipMemcpyDeviceToHost));
+        if (d <= -2) {
+          const std::vector<int> pr = peer_ranks();
+          const int sd = (-2 - d) / RP_MAX;
+          std::fprintf(stderr, " [%d: rank %d's tile %d, word now %u]", l, sd < (int)pr.size() ? pr[(size_t)sd] : -1, (-2 - d) % RP_MAX, seen);
+        } else {
+          std::fprintf(stderr, " [%d: own tile %d, word now %u]", l, d, seen);
+        }
+      }
+    std::fprintf(stderr, "\n");
+  }
+  std::fprintf(stderr, "cice4_amd: resident EVP loop timed out (not every tile was resident%s); this range runs as one "
+                       "launch per pair of subcycles%s\n", peer ? ", here or on another rank" : "",
+               dense ? ", later ones with one workgroup per CU" : " and so do later ones");
+  if (dense) res_level = 1;   // not every slot of the chip was free: one workgroup per CU from now on
+  else resident_failed = true;
+  // whoever held the slots may be gone later: look again after res_retry_steps calls (across ranks only where the
+  // ranks agreed on the time-out, so that they also agree on the retry)
+  res_retry_in = (!peer || res_peer_agree) ? res_retry_steps : 0;
+  res_prog.zero(stream);
+  if (res_prog2.p) res_prog2.zero(stream);
+  if (!peer && res_xg.p) res_xg.zero(stream);
+  if (!peer && res_xgr.p) res_xgr.zero(stream);
+  if (!peer) res_epoch = 0;   // (across ranks the neighbours hold words about us: the epoch only ever grows)
+}
+
+// Host only, no device: what retire_resident does with n pending records, oldest first.  word0[k]: the abort word launch k
+// read back; cur / flips / ident[k]: the state launch k found.  out = {records in front of the first that gave up (their ice
+// cover counts), ranges to run again (that one and ALL behind it, whatever their own words say: they began under its abort
+// word), then cur, flips, copies_identical to go on from -- the logged ones of the launch that gave up, else the present ones}
+void evp_resident_plan(int n, const unsigned* word0, const int* cur, const int* flips, const int* ident, int cur_now, int flips_now,
+                       int ident_now, int out[5]) {
+  int k = 0;
+  while (k < n && word0[k] == 0u) ++k;
+  out[0] = k;
+  out[1] = n - k;
+  out[2] = k < n ? cur[k] : cur_now;
+  out[3] = k < n ? flips[k] : flips_now;
+  out[4] = k < n ? ident[k] : ident_now;
+}
+
+// Looks at the records of the launches queued so far, oldest first.  A clean record: the ice cover it carries steers the
+// shape of later calls, nothing else.  The first record with the abort word set: that launch gave up, and every launch
+// queued behind it found the word set when it began and left at once (k_evp_resident: the first thing a workgroup does).
+// A loop that gives up leaves the caller's state untouched -- the inputs are only read, results go to the other copy
+// behind the last subcycle -- so cur, flips and copies_identical go back to what they were before that launch, its range
+// runs through the other loops, and the ranges behind it run as the calls they were: what a wait per call would have left.
+// Nothing a launch that left at once has written is read here: the exchange copies (res_xu) are filled again by the next
+// launch of the loop, the granule copies and the progress words are zeroed with the epoch (resident_gave_up), and neither
+// launch_range nor a captured graph reads any of them.
+void Evp::retire_resident() {
+  if (res_pending.empty()) return;
+  CICE_HIP(hipStreamSynchronize(stream));
+  std::vector<ResPending> pend;
+  pend.swap(res_pending);
+  struct Sync { bool& d; bool was; ~Sync() { d = was; } } sync{res_defer, res_defer};   // whatever runs again here waits for its launch
+  res_defer = false;
+  std::vector<unsigned> word0(pend.size());
+  std::vector<int> curs(pend.size()), flps(pend.size()), idents(pend.size());
+  for (size_t q = 0; q < pend.size(); ++q) {
+    word0[q] = res_why[8 * (size_t)pend[q].slot];
+    curs[q] = pend[q].cur; flps[q] = pend[q].flips; idents[q] = pend[q].copies_identical ? 1 : 0;
+  }
+  int plan[5];
+  evp_resident_plan((int)pend.size(), word0.data(), curs.data(), flps.data(), idents.data(), cur, flips, copies_identical ? 1 : 0, plan);
+  size_t k = 0;
+  for (; k < (size_t)plan[0]; ++k) resident_cover(res_why[8 * (size_t)pend[k].slot + 7], pend[k].map);
+  if (plan[1] == 0) return;
+  resident_gave_up(res_why + 8 * (size_t)pend[k].slot, pend[k].dense, false);
+  cur = plan[2];
+  flips = plan[3];
+  copies_identical = plan[4] != 0;
+  run_range(pend[k].ksub0, pend[k].nsub, nullptr, false);
+  for (++k; k < pend.size(); ++k) run_range(pend[k].ksub0, pend[k].nsub, nullptr, true);
+}
+
+// subcycles ksub0 .. ksub0+nsub-1 in one launch; false: not done (time-out), the state is as it was.  With res_defer (one
+// rank): true once the launch is queued -- whether it ran to the end is found out by retire_resident
 bool Evp::run_resident(int ksub0, int nsub) {
   const bool peer = halo.multi_rank();
   const int W = resident_waves();
@@ -5673,11 +5798,7 @@ bool Evp::run_resident(int ksub0, int nsub) {
   const dim3 g(8 * ((res_tiles + 7) / 8));
   const bool damp = sc.evp_damping != 0;
   {   // every workgroup of the launch has to be resident at once
-    int ncu = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-    }
+    const int ncu = device_cus();
     const int per_cu = resident_occupancy(W, damp, peer);
     if ((long long)per_cu * ncu < (long long)g.x) {
       std::fprintf(stderr, "cice4_amd: resident EVP loop not used: %u workgroups of %d wavefronts, the device holds %d x %d "
@@ -5700,11 +5821,7 @@ bool Evp::run_resident(int ksub0, int nsub) {
     if (res_map.n == 0) { res_map.alloc(4); res_map_stale = true; }
     if (res_map_stale) {
       static const int force = [] { const char* e = std::getenv("CICE4_AMD_RESIDENT_MAP"); return e ? std::atoi(e) : -1; }();
-      int ncu = 256, dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-      }
+      const int ncu = device_cus();
       hipLaunchKernelGGL(k_res_choose_map, dim3(1), dim3(1024), 0, stream, r.a.tiles_x * r.a.tiles_y * r.a.nblocks, r.a.tiles_x,
                          r.a.tiles_y, W, dom.nx_block, dom.ny_block, std::max(1, ncu / 8), res_map_opt >= 0 ? res_map_opt : force,
                          (const int32_t*)blk.p, (const int32_t*)icetmask.p, (const int32_t*)iceumask.p, res_map.p, r.abort_flag + 7);
@@ -5713,11 +5830,7 @@ bool Evp::run_resident(int ksub0, int nsub) {
     r.tile_map = res_map.p;
   }
   {
-    int ncu = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-    }
+    const int ncu = device_cus();
     r.prio_div = std::max(1, ncu / 8);
   }
   r.stamps = stamp_buffer(3 * (size_t)g.x + 600);       // [4 g] stamps, then [8 g] phase sums, then [2400] the trace of a few tiles (GRAN)
@@ -5742,7 +5855,22 @@ bool Evp::run_resident(int ksub0, int nsub) {
     resident_failed = true;
     return false;
   }
-  unsigned aborted = 0;
+  // one read-back per loop: the abort word, who gave up on what, and (word 7) the ice cover k_res_choose_map counted --
+  // into page-locked memory (a copy into pageable memory is staged and synchronous: ~15 us of a 600-us loop)
+  if (!res_why) CICE_HIP(hipHostMalloc((void**)&res_why, (RES_RING + 1) * 8 * sizeof(unsigned), hipHostMallocDefault));
+  if (res_defer && !peer) {
+    // nothing here needs the record before the next launch may be queued: it goes into a slot of its own, and the state
+    // moves on as it does after a loop that ran to the end (retire_resident takes that back where it did not)
+    const int slot = (int)res_pending.size();
+    CICE_REQUIRE(slot < RES_RING, "resident EVP loop: more launches pending than records");
+    CICE_HIP(hipMemcpyAsync(res_why + 8 * (size_t)slot, r.abort_flag, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    res_pending.push_back(ResPending{ksub0, nsub, cur, flips, copies_identical, dense, r.tile_map != nullptr, res_epoch, slot});
+    res_epoch += (unsigned)nsub;
+    cur = 1 - cur;
+    ++flips;
+    copies_identical = false;
+    return true;
+  }
   if (peer) {
     // This loop ends when the neighbours' loops have run: nothing here may block inside the runtime before they are
     // launched.  Ranks that are threads of ONE process (the one-GPU tests) share the runtime's locks, and a blocking copy
@@ -5754,62 +5882,13 @@ bool Evp::run_resident(int ksub0, int nsub) {
     CICE_HIP(q);
   }
   if (peer && res_peer_agree) halo.all_max_u32(r.abort_flag);   // every rank falls back, or none does
-  // one read-back per loop: the abort word, who gave up on what, and (word 7) the ice cover k_res_choose_map counted --
-  // into page-locked memory (a copy into pageable memory is staged and synchronous: ~15 us of a 600-us loop)
-  if (!res_why) CICE_HIP(hipHostMalloc((void**)&res_why, 8 * sizeof(unsigned), hipHostMallocDefault));
-  unsigned* why = res_why;
+  unsigned* why = res_why + 8 * (size_t)RES_RING;
   CICE_HIP(hipMemcpyAsync(why, r.abort_flag, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   CICE_HIP(hipStreamSynchronize(stream));
-  const int cover[3] = {0, (int)(why[7] >> 16), (int)(why[7] & 0xffffu)};
-  if (r.tile_map && cover[2] > 0) {
-    // Which shape the NEXT call takes (granules_on): under an ice cover that leaves most tiles empty three barrier-coupled
-    // workgroups per CU win -- a CU then holds one tile with ice and two without (gx1 size, polar caps: 231 k subcycles/s
-    // against 205 k for the granule loop; fully covered 186 k against 200 k).  The cover of one step is the cover of the
-    // next to within a few cells; hysteresis keeps the tables from being rebuilt back and forth.
-    const int pct = (int)(100LL * cover[1] / cover[2]);
-    if (pct < 50) res_sparse = true;
-    else if (pct > 60) res_sparse = false;
-  }
-  aborted = why[0];
+  resident_cover(why[7], r.tile_map != nullptr);
   res_epoch += (unsigned)nsub + (peer ? 3u : 0u);
-  if (aborted && why[1]) {   // this rank's own first time-out (none: the word came from another rank)
-    std::fprintf(stderr, "cice4_amd: rank %d: tile %u of %d gave up %s (subcycle %u of the launch, word wanted %u), producers "
-                         "not heard from: lanes %08x%08x of its dependency list:", dom.rank, why[2], res_tiles,
-                 why[1] == 1 ? "waiting for the neighbouring ranks' loops to begin" : why[1] == 4 ? "polling the granules of its halo" : "waiting for the producers of its halo",
-                 why[3], why[6], why[5], why[4]);
-    std::vector<int32_t> dl(RES_MAXDEP);
-    CICE_HIP(hipMemcpy(dl.data(), res_deps.p + (size_t)why[2] * RES_MAXDEP, RES_MAXDEP * 4, hipMemcpyDeviceToHost));
-    const unsigned long long ms = ((unsigned long long)why[5] << 32) | why[4];
-    for (int l = 0; l < RES_MAXDEP; ++l)
-      if ((ms >> l) & 1) {
-        unsigned seen = 0;
-        const int d = dl[l];
-        const unsigned* wp = d <= -2 ? res_rprog.p + (size_t)(-2 - d) * RES_STRIDE : res_prog.p + (size_t)d * RES_STRIDE;
-        CICE_HIP(hipMemcpy(&seen, wp, 4, hipMemcpyDeviceToHost));
-        if (d <= -2) {
-          const std::vector<int> pr = peer_ranks();
-          const int sd = (-2 - d) / RP_MAX;
-          std::fprintf(stderr, " [%d: rank %d's tile %d, word now %u]", l, sd < (int)pr.size() ? pr[(size_t)sd] : -1, (-2 - d) % RP_MAX, seen);
-        } else {
-          std::fprintf(stderr, " [%d: own tile %d, word now %u]", l, d, seen);
-        }
-      }
-    std::fprintf(stderr, "\n");
-  }
-  if (aborted) {
-    std::fprintf(stderr, "cice4_amd: resident EVP loop timed out (not every tile was resident%s); this range runs as one "
-                         "launch per pair of subcycles%s\n", peer ? ", here or on another rank" : "",
-                 dense ? ", later ones with one workgroup per CU" : " and so do later ones");
-    if (dense) res_level = 1;   // not every slot of the chip was free: one workgroup per CU from now on
-    else resident_failed = true;
-    // whoever held the slots may be gone later: look again after res_retry_steps calls (across ranks only where the
-    // ranks agreed on the time-out, so that they also agree on the retry)
-    res_retry_in = (!peer || res_peer_agree) ? res_retry_steps : 0;
-    res_prog.zero(stream);
-    if (res_prog2.p) res_prog2.zero(stream);
-    if (!peer && res_xg.p) res_xg.zero(stream);
-    if (!peer && res_xgr.p) res_xgr.zero(stream);
-    if (!peer) res_epoch = 0;   // (across ranks the neighbours hold words about us: the epoch only ever grows)
+  if (why[0]) {
+    resident_gave_up(why, dense, peer);
     return false;
   }
   cur = 1 - cur;   // the result is in the other copy whatever the parity of nsub
@@ -5882,12 +5961,36 @@ void Evp::launch_range(int ksub0, int nsub) {
 void Evp::subcycles(int ksub0, int nsub, float* elapsed_ms) {
   CICE_REQUIRE(prepared, "cice_evp_subcycles before cice_evp_prepare");
   CICE_REQUIRE(ksub0 >= 1 && nsub >= 0, "bad subcycle range");
+  // An untimed range that goes to the one-launch loop of a one-rank domain is queued behind the launches still pending
+  // (their outcome taken for granted: can_reside() as they left it); every other call first brings the object to where
+  // a wait per launch would have left it.  So does a call that finds RES_RING launches pending, or tables to be built.
+  static const bool env_sync = [] { const char* e = std::getenv("CICE4_AMD_RESIDENT_ASYNC"); return e && e[0] == '0'; }();
+  auto queued = [&] { return res_async && !env_sync && !elapsed_ms && nsub >= 2 && !halo.multi_rank() && can_reside(); };
+  bool defer = queued();
+  // (nor is the progress epoch reset under pending launches: the reset clears the abort word with the progress words, and a
+  //  launch queued behind a loop that gave up has to find that word set)
+  if (!res_pending.empty() && (!defer || (int)res_pending.size() >= RES_RING || !resident_tables_current() || res_epoch > 0x70000000u)) {
+    retire_resident();
+    defer = queued();
+  }
+  res_defer = defer;
+  try {
+    run_range(ksub0, nsub, elapsed_ms, true);
+  } catch (...) {
+    res_defer = false;
+    throw;
+  }
+  res_defer = false;
+}
+
+// (retire_resident runs a range again through this: res_defer is off then, and try_resident for the range that gave up)
+void Evp::run_range(int ksub0, int nsub, float* elapsed_ms, bool try_resident_loop) {
   // elapsed_ms: events that live as long as the object (creating and destroying a pair per call, and four records instead of
   // two, cost a step of the one-launch loop 20 us of its 600: scripts/step_overhead.py).  The one-launch loop is timed around
   // its ONE launch -- what rocprofv3 reports for the kernel -- not around the small launch that chooses the tile map before it
   // and the read-back of the abort word behind it (run_resident); every other form of the range around all its launches.
   hipEvent_t &e0 = sub_t0, &e1 = sub_t1;
-  const bool try_resident = nsub >= 2 && (can_reside() || can_reside_peer());
+  const bool try_resident = try_resident_loop && nsub >= 2 && (can_reside() || can_reside_peer());
   if (elapsed_ms) {
     for (hipEvent_t* e : {&sub_t0, &sub_t1, &res_t0, &res_t1})
       if (!*e) CICE_HIP(hipEventCreate(e));
@@ -5934,6 +6037,10 @@ void Evp::subcycles(int ksub0, int nsub, float* elapsed_ms) {
     replayed = run_resident(ksub0, nsub);
     if (replayed) loop_launches = 1;
     else res_timed = false;
+    if (!replayed && !res_pending.empty()) {   // nothing was launched: what is pending comes first, and may run again
+      retire_resident();
+      loop_launches = 0;
+    }
     if (!replayed && elapsed_ms) CICE_HIP(hipEventRecord(e0, stream));   // (the loop gave up: the other loops run the range)
   }
   res_time_it = false;
@@ -6005,6 +6112,9 @@ void Evp::subcycles(int ksub0, int nsub, float* elapsed_ms) {
 
 void Evp::finish() {
   CICE_REQUIRE(prepared, "cice_evp_finish before cice_evp_prepare");
+  // The one retire inside the class: finish() follows a queued subcycles() within ONE entry (step, run).  Everywhere else
+  // the rule is the C-ABI's -- CICE_TRY retires before anything of the entry runs (capi.hip) -- and a new entry gets it from there.
+  retire_resident();   // k_finish reads the velocities the loop left: of a loop that ran to the end, or of the loops run in its place
   PrepArgs a{};
   a.nx = dom.nx_block; a.ny = dom.ny_block; a.nblocks = dom.nblocks(); a.n = n; a.blk = blk.p;
   a.iceumask = iceumask.p; a.uocn = uocn.p; a.vocn = vocn.p; a.u = uv[cur].p; a.v = uv[cur].p + n;

@@ -220,7 +220,12 @@ int cice_evp_download(cice_ctx *ctx, cice_evp_fields *f);       /* io + out fiel
  * ksub == ndte also writes divu, shear, rdg_conv, rdg_shear, prs_sig, strint, strocn); finish = :410-428.
  * elapsed_ms (may be NULL) is the HIP-event time of the launches on the library's stream; where the range runs as the one-launch
  * loop, of that ONE launch (what rocprofv3 reports for the kernel), without the small launch that picks the tile map in front
- * of it and the read-back of the abort word behind it. */
+ * of it and the read-back of the abort word behind it.
+ * A call with elapsed_ms == NULL whose range runs as the one-launch loop on a one-rank domain returns as soon as the launch is
+ * queued (option "resident_async", below): whether the loop ran to the end is looked at by the next call of ANY other entry
+ * of this context -- and by cice_evp_get_info for any key but "resident_pending" -- which then finds everything as a wait
+ * behind every loop would have left it: results, "resident", "last_launches", a time-out message.  At most 16 launches are
+ * pending at a time. */
 int cice_evp_prepare(cice_ctx *ctx, double dt);
 int cice_evp_subcycles(cice_ctx *ctx, int ksub0, int nsub, float *elapsed_ms);
 int cice_evp_finish(cice_ctx *ctx);
@@ -236,6 +241,10 @@ int cice_evp_finish(cice_ctx *ctx);
  * overlap the arithmetic of the others; a launch that does not get every slot times out and later ones use one workgroup
  * per compute unit), "resident_spin_us" (default 200000: how long a tile of the resident loop waits for a neighbour
  * before the launch gives up and the range is run by the launch-per-pair loop; 0 makes every wait fail -- tests),
+ * "resident_async" (0/1, default 1; environment CICE4_AMD_RESIDENT_ASYNC=0: one-launch loops of a one-rank domain are queued
+ * back to back -- the abort record of a launch is read back into a slot of its own and looked at later, see
+ * cice_evp_subcycles; a loop found to have given up, and every range queued behind it, is then run again from the state the
+ * loop left untouched; 0 waits behind every launch -- A/B runs),
  * "resident_map" (-1 default: which tile a workgroup of that loop takes is chosen on the device, once per evp(dt), by the ice
  * cover -- under ice in latitude bands a CU gets one tile with ice and two without; 0 / 1 fix the map).
  * Sweeps (K subcycles per launch on grids of ~0.1 degree size): "skew" (0/1), "skew_levels" (K: 2, 3, 4 default; 5, 6, 8 in -DCICE4_AMD_EXPERIMENTS builds),
@@ -266,7 +275,8 @@ int cice_evp_finish(cice_ctx *ctx);
  * compute unit), "resident_granules" (1 if with the granule hand-off), "resident_map" (the map last chosen, -1 before the first loop), "skew" / "skew_fold" (1 if sweeps apply), "skew_joined" (1 if they run on a joined image of several blocks; with "skew_fold" also 1: under a tripole fold), "skew_join_fold" (the option read back),
  * "skew_levels", "skew_strips", "skew_seg_rows", "skew_rowact", "skew_balance", "skew_balanced" (sweeps measured so far),
  * "skew_fill", "skew_pairs", "skew_subs", "skew_split", "skew_trim_ext", "last_launches" (kernel launches of the last
- * subcycle range: 1 = the one-launch loop). */
+ * subcycle range: 1 = the one-launch loop), "resident_pending" (one-launch loops queued whose outcome has not been looked
+ * at yet; the one key that does not look). */
 int cice_evp_set_option(cice_ctx *ctx, const char *key, int value);
 int cice_evp_get_info(cice_ctx *ctx, const char *key, int *value);
 /* number of T-cells with icetmask = 1 and U-cells with iceumask on this rank after prepare
@@ -527,6 +537,12 @@ int cice_transport_remap(cice_ctx *ctx, double dt, const cice_transport_fields *
  * gives up so that every owned column comes out right (checked by a lane-level restatement of the kernel's dependencies),
  * -1 if there is none; *strips = column strips of the block. */
 int cice_debug_skew_layout(int K, int S, int ncol, int cyclic, int *strips);
+/* Test aid, needs no device: the bookkeeping of the retire of n pending one-launch loops (option "resident_async"), oldest
+ * first.  word0[k]: the abort word launch k read back; cur / flips / ident[k]: buffer parity, swap count and "copies identical"
+ * as launch k found them; *_now: the present ones.  out = {records in front of the first that gave up, ranges run again (that
+ * one and all behind it, whatever their own words say), cur, flips, copies_identical to go on from}. */
+int cice_debug_resident_plan(int n, const uint32_t *word0, const int32_t *cur, const int32_t *flips, const int32_t *ident,
+                             int cur_now, int flips_now, int ident_now, int32_t out[5]);
 /* Test aid, needs no device: the cell map of the image that a ONE-TASK domain of several blocks (cice_domain_create with these
  * arguments, one task) is joined into for the K-subcycle sweeps (option "skew_join"): an image of (nxg + 2) x (nyg + 2) cells,
  * row-major, 0-based.  map[cell of the (nblocks, ny_block, nx_block) block arrays] = the image cell that holds the cell's
