@@ -57,6 +57,17 @@ __device__ __forceinline__ size_t lvl(const TransportKernelArgs& a, int level) {
 // level of tracer nt (0-based) of category n (1-based) in tm / tmask / tc / tx / ty
 __device__ __forceinline__ int tl(const TransportKernelArgs& a, int n, int nt) { return (n - 1) * a.ntrace + nt; }
 
+// The failure report: one atomicMin over a key ordered the way the reference meets its failures.  All departure checks
+// come before any area check (horizontal_remap :560-665, then :701-879): code 1 before code 2; the first failing block
+// ends the run; within a block open water (:830-848) comes before the categories in order (:855-875); and within one
+// check the reference overwrites istop, jstop at every failing cell (departure_points :1640-1655, update_fields
+// :3756-3772), so it names the LAST failing cell in j-then-i order: the low bits count cells from the end of the plane.
+__device__ __forceinline__ unsigned long long stop_key(const TransportKernelArgs& a, int code, int b, int n, size_t q) {
+  const size_t np = (size_t)a.nx * a.ny;
+  return ((unsigned long long)code << 60) | ((unsigned long long)b << 40) | ((unsigned long long)n << 32) |
+         (unsigned long long)(np - 1 - q);
+}
+
 // ---- state_to_tracers (driver :847-1003) + make_masks (:891-1059) ------------------------------------
 __global__ __launch_bounds__(256) void k_tr_tracers(const TransportKernelArgs a) {
   Cell k;
@@ -202,7 +213,7 @@ __global__ __launch_bounds__(256) void k_tr_departure(const TransportKernelArgs 
     dpx = -a.dt * u;
     dpy = -a.dt * v;
     if (dpx < -a.HTN[c] || dpx > a.HTN[c + 1] || dpy < -a.HTE[c] || dpy > a.HTE[c + nx])
-      atomicMin(a.errkey, ((unsigned long long)1 << 60) | ((unsigned long long)k.b << 40) | (unsigned long long)k.q);
+      atomicMin(a.errkey, stop_key(a, 1, k.b, 0, k.q));
     if (u != c0 || v != c0) {
       dpx = dpx / a.dxu[c];
       dpy = dpy / a.dyu[c];
@@ -507,8 +518,7 @@ __global__ __launch_bounds__(256) void k_tr_update(const TransportKernelArgs a) 
   double w1 = fe[k.c] - fe[k.c - 1] + fn[k.c] - fn[k.c - a.nx];
   double m = mold - w1 * told;
   if (m < -puny) {   // negative area: the caller aborts (:3722-3744)
-    atomicMin(a.errkey, ((unsigned long long)2 << 60) | ((unsigned long long)k.b << 40) | ((unsigned long long)n << 32) |
-                            (unsigned long long)k.q);
+    atomicMin(a.errkey, stop_key(a, 2, k.b, n, k.q));
     return;
   }
   if (m < c0) m = c0;
@@ -743,7 +753,7 @@ void Transport::remap(double dt, const cice_transport_fields& f, int32_t* l_stop
   if (istop) *istop = 0;
   if (jstop) *jstop = 0;
   if (hk != ~0ull) {   // 1: departure points out of bounds, 2: negative area
-    const size_t q = (size_t)(hk & 0xffffffffull);
+    const size_t q = np - 1 - (size_t)(hk & 0xffffffffull);   // (stop_key counts cells from the end of the plane)
     if (l_stop) *l_stop = (int32_t)(hk >> 60);
     if (jstop) *jstop = (int32_t)(q / dom.nx_block) + 1;
     if (istop) *istop = (int32_t)(q % dom.nx_block) + 1;

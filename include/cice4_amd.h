@@ -516,7 +516,11 @@ int cice_frzmlt_bottom_lateral(cice_ctx *ctx, int nx_block, int ny_block, int il
  * tracers_to_state and bound_state, all on the device; host arrays in the reference's layout: aice0, uvel, vvel
  * (nx,ny,nb), aicen/vicen/vsnon (nx,ny,ncat,nb), trcrn (nx,ny,max_ntrcr,ncat,nb), eicen (nx,ny,ntilyr,nb),
  * esnon (nx,ny,ntslyr,nb).  l_stop: 0 ok, 1 departure point outside the neighbouring cells, 2 negative area
- * (the caller's abort_ice), with a cell (istop, jstop).  Compile-time choices of the reference kept:
+ * (the caller's abort_ice), with a cell (istop, jstop): the cell the reference prints before abort_ice.  Rule: a
+ * departure failure before any area failure; the first failing block; in it open water before the categories in order;
+ * of the cells that fail that one check the LAST in j-then-i order (the reference overwrites istop, jstop at every
+ * failing cell, ice_transport_remap.F90:1640-1655, 3756-3772).  The state arrays of a failed call are not defined.
+ * Compile-time choices of the reference kept:
  * l_fixed_area = F, integral_order = 3, l_dp_midpt = T.  advection = 'upwind' is not provided. */
 typedef struct {
   int ntrcr;

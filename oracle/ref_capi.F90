@@ -759,6 +759,22 @@ contains
       done = .true.
    end subroutine ref_init_transport
 
+   ! the same with the caller's tracer set: ntrcr tracers, trcr_depend(1:ntrcr) each 0 (ice area), 1 (ice volume) or
+   ! 2 (snow volume).  nt_Tsfc = 1 and nt_iage = 2 stay as ref_boot set them.  The reference allocates its tracer tables
+   ! once (init_transport :109): one tracer set per process, later calls are ignored like those of ref_init_transport.
+   subroutine ref_init_transport_set(ntrcr_in, depend_in) bind(C, name='ref_init_transport_set')
+      use ice_transport_driver, only: init_transport, advection, tracer_type
+      use ice_state, only: ntrcr, trcr_depend
+      integer(c_int), value :: ntrcr_in
+      integer(c_int), intent(in) :: depend_in(ntrcr_in)
+      if (allocated(tracer_type)) return
+      advection = 'remap'
+      ntrcr = ntrcr_in
+      trcr_depend(:) = 0
+      trcr_depend(1:ntrcr) = depend_in(1:ntrcr)
+      call init_transport
+   end subroutine ref_init_transport_set
+
    ! pieces of transport_remap for stage-by-stage comparisons: state_to_tracers for every local block, and
    ! horizontal_remap on caller-supplied mean fields (module uvel, vvel); edgearea_* come back (l_fixed_area = F)
    subroutine ref_state_to_tracers(aim, trm) bind(C, name='ref_state_to_tracers')

@@ -283,8 +283,12 @@ class Ref:
     def halo_i4(self, a, loc=1, kind=1):
         self.lib.ref_halo_i4(_p(a), C.c_int(loc), C.c_int(kind))
 
-    def init_transport(self):
-        self.lib.ref_init_transport()
+    def init_transport(self, ntrcr=2, trcr_depend=(0, 1)):
+        """init_transport (ice_transport_driver.F90:81) for `ntrcr` tracers with the given trcr_depend (0 ice area,
+        1 ice volume, 2 snow volume).  The reference allocates its tracer tables once: ONE tracer set per process."""
+        dep = i4(list(trcr_depend))
+        assert 1 <= ntrcr <= MAX_NTRCR and dep.shape == (ntrcr,) and all(0 <= d <= 2 for d in dep)
+        self.lib.ref_init_transport_set(C.c_int(ntrcr), _p(dep))
 
     def state_to_tracers(self, ntrace=9):
         aim = np.zeros((self.max_blocks, NCAT + 1, self.ny_block, self.nx_block))

@@ -2,7 +2,9 @@
 `call transport_remap(dt)` of the compiled reference (source/ice_transport_driver.F90:179,
 source/ice_transport_remap.F90:328), one process per configuration (tests/transport_case.py): 2 x 2 and padded
 3 x 3 blocks, cyclic / open edges, tripole north boundary, and the real gx3 grid and land mask cut into 120 blocks
-with the all-land ones eliminated.  Every state array incl. ghost cells, three flow / ice-cover regimes: bit for bit.
+with the all-land ones eliminated.  Every state array incl. ghost cells, three flow / ice-cover regimes, each stepped twice
+(the second step from the state the first produced): bit for bit; trcrn's planes beyond ntrcr untouched.  Other tracer
+sets (ntrcr 1, 3, 5; snow-volume tracers) on the smallest grids; the failure reports against a reference-minted fixture.
 The same configurations for advection = 'upwind' (cice_transport_upwind against `call transport_upwind(dt)`, :672)."""
 import os
 import subprocess
@@ -39,6 +41,72 @@ def test_transport_upwind_equals_reference(case):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "transport_case.py"), *args],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "TRANSPORT-OK" in p.stdout, p.stdout[-1500:] + p.stderr[-4000:]
+
+
+# Tracer sets other than (Tsfc, iage): ntrcr = 1; area, ice-volume and snow-volume tracers together; ntrcr = 5 (the per-thread
+# tracer arrays full, every enthalpy level moved) with two tracers on hsno, also on padded blocks and across the fold.
+TRC_CASES = [(("small", "cyclic", "open"), (0,)), (("small", "cyclic", "open"), (0, 1, 2)),
+             (("small", "cyclic", "open"), (0, 2, 2, 1, 0)), (("pad", "open", "open"), (0, 2, 2, 1, 0)),
+             (("small", "cyclic", "tripole"), (0, 2, 2, 1, 0))]
+_trc_id = lambda c: "-".join(c[0]) + "-trc" + "".join(str(d) for d in c[1])
+
+
+def _run_tracer_case(case, trc, upwind):
+    from oracle import refapi
+    if not refapi.available(case[0]):
+        pytest.skip(f"oracle/_ref/libcice_ref_{case[0]}.so not built")
+    args = list(case) + ["-", "upwind" if upwind else "-", "trc=" + ",".join(str(d) for d in trc)]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "transport_case.py"), *args],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "TRANSPORT-OK" in p.stdout, p.stdout[-1500:] + p.stderr[-4000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", TRC_CASES, ids=_trc_id)
+def test_transport_remap_tracer_sets_equal_reference(case):
+    _run_tracer_case(case[0], case[1], upwind=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [c for c in TRC_CASES if c[0][1] != "open"], ids=_trc_id)
+def test_transport_upwind_tracer_sets_equal_reference(case):
+    _run_tracer_case(case[0], case[1], upwind=True)
+
+
+def _stop_fixture_ready():
+    from oracle import refapi
+    return refapi.available("small")
+
+
+def test_transport_stop_fixture_is_what_the_reference_reports():
+    """Re-mint tests/golden/transport_stop.npz from the compiled reference (no GPU: the reference alone, one child process per
+    case) and compare with the committed file -- the reported cells, the printed figures and the checksum of the inputs, so
+    the GPU test below provably feeds the library the inputs the reference was given."""
+    if not _stop_fixture_ready():
+        pytest.skip("oracle/_ref/libcice_ref_small.so not built")
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("make_golden_transport_stop",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_transport_stop.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    new = m.mint()
+    old = np.load(os.path.join(ROOT, "tests", "golden", "transport_stop.npz"))
+    assert set(new) | {"meta"} == set(old.files)
+    for k, v in new.items():
+        assert np.array_equal(old[k], v), (k, old[k], v)
+
+
+@pytest.mark.gpu
+def test_transport_stop_report_names_the_reference_cell():
+    """(l_stop, istop, jstop) of cice_transport_remap for departure points out of bounds, negative open water, a negative
+    category area and both kinds at once = the cell the reference printed (tests/golden/transport_stop.npz; cases and what
+    each wrong ordering would return: tests/transport_stop_case.py); then a good call on the same context, bit for bit."""
+    if not _stop_fixture_ready():
+        pytest.skip("oracle/_ref/libcice_ref_small.so not built")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "transport_stop_case.py"), "gpu"],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "TRANSPORT-STOP-OK" in p.stdout, p.stdout[-1500:] + p.stderr[-4000:]
 
 
 @pytest.mark.gpu
