@@ -444,6 +444,87 @@ module cice4_amd_c
       end function
    end interface
 
+   ! thermodynamic changes of the thickness distribution (source/ice_therm_itd.F90; cice4_amd/csrc/itd.hip)
+   type, bind(C) :: cice_itd_config
+      integer(c_int) :: ntrcr
+      integer(c_int) :: trcr_depend(5)
+      integer(c_int) :: nt_Tsfc, nt_iage, nt_alvl, nt_vlvl
+      integer(c_int) :: tr_iage, tr_lvl, update_ocn_f
+      real(c_double) :: hin_max(6)
+      real(c_double) :: hi_min
+   end type
+
+   type, bind(C) :: cice_therm2_fields
+      integer(c_int) :: ncat, kitd, state_resident
+      type(c_ptr) :: aicen, trcrn, vicen, vsnon, eicen, esnon
+      type(c_ptr) :: aicen_init = c_null_ptr, vicen_init
+      type(c_ptr) :: frain, frzmlt, Tf, rside
+      type(c_ptr) :: tmask
+      type(c_ptr) :: aice, aice0, fresh, fsalt, fhocn, frazil, meltl, frz_onset
+   end type
+
+   interface
+      integer(c_int) function cice_itd_init(ctx, cfg) bind(C, name='cice_itd_init')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_itd_config), intent(in) :: cfg
+      end function
+      integer(c_int) function cice_linear_itd(ctx, nx_block, ny_block, icells, indxi, indxj, ntrcr, trcr_depend, &
+            aicen_init, vicen_init, aicen, trcrn, vicen, vsnon, eicen, esnon, aice, aice0, l_stop, istop, jstop, &
+            n_not_remapped) bind(C, name='cice_linear_itd')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, icells, ntrcr
+         integer(c_int), intent(in) :: indxi(*), indxj(*), trcr_depend(*)
+         real(c_double), intent(in) :: aicen_init(*), vicen_init(*)
+         real(c_double), intent(inout) :: aicen(*), trcrn(*), vicen(*), vsnon(*), eicen(*), esnon(*), aice(*), aice0(*)
+         integer(c_int), intent(out) :: l_stop, istop, jstop
+         integer(c_long_long), intent(out) :: n_not_remapped
+      end function
+      integer(c_int) function cice_add_new_ice(ctx, nx_block, ny_block, ntrcr, icells, indxi, indxj, tmask, dt, aicen, &
+            trcrn, vicen, eicen, aice0, aice, frzmlt, frazil, frz_onset, yday, fresh, fsalt, Tf, l_stop, istop, jstop) &
+            bind(C, name='cice_add_new_ice')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, ntrcr, icells
+         integer(c_int), intent(in) :: indxi(*), indxj(*), tmask(*)
+         real(c_double), value :: dt, yday
+         real(c_double), intent(inout) :: aicen(*), trcrn(*), vicen(*), eicen(*), aice0(*), frazil(*), frz_onset(*), &
+                                          fresh(*), fsalt(*)
+         real(c_double), intent(in) :: aice(*), frzmlt(*), Tf(*)
+         integer(c_int), intent(out) :: l_stop, istop, jstop
+      end function
+      integer(c_int) function cice_lateral_melt(ctx, nx_block, ny_block, ilo, ihi, jlo, jhi, dt, fresh, fsalt, fhocn, &
+            rside, meltl, aicen, vicen, vsnon, eicen, esnon) bind(C, name='cice_lateral_melt')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, ilo, ihi, jlo, jhi
+         real(c_double), value :: dt
+         real(c_double), intent(inout) :: fresh(*), fsalt(*), fhocn(*), meltl(*), aicen(*), vicen(*), vsnon(*), &
+                                          eicen(*), esnon(*)
+         real(c_double), intent(in) :: rside(*)
+      end function
+      integer(c_int) function cice_shift_ice(ctx, nx_block, ny_block, indxi, indxj, icells, ntrcr, trcr_depend, aicen, &
+            trcrn, vicen, vsnon, eicen, esnon, hicen, donor, daice, dvice, l_stop, istop, jstop) &
+            bind(C, name='cice_shift_ice')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, icells, ntrcr
+         integer(c_int), intent(in) :: indxi(*), indxj(*), trcr_depend(*), donor(*)
+         real(c_double), intent(inout) :: aicen(*), trcrn(*), vicen(*), vsnon(*), eicen(*), esnon(*), hicen(*), &
+                                          daice(*), dvice(*)
+         integer(c_int), intent(out) :: l_stop, istop, jstop
+      end function
+      integer(c_int) function cice_step_therm2_itd(ctx, dt, yday, f, l_stop, istop, jstop, bstop, stage) &
+            bind(C, name='cice_step_therm2_itd')
+         import
+         type(c_ptr), value :: ctx
+         real(c_double), value :: dt, yday
+         type(cice_therm2_fields), intent(in) :: f
+         integer(c_int), intent(out) :: l_stop, istop, jstop, bstop, stage
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

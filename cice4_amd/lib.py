@@ -90,6 +90,20 @@ class AtmoFields(C.Structure):
                [(n, C.c_void_p) for n in ("strairxn", "strairyn", "Trefn", "Qrefn", "lhcoef", "shcoef")]
 
 
+class ItdConfig(C.Structure):
+    _fields_ = [("ntrcr", C.c_int), ("trcr_depend", C.c_int * 5), ("nt_Tsfc", C.c_int), ("nt_iage", C.c_int),
+                ("nt_alvl", C.c_int), ("nt_vlvl", C.c_int), ("tr_iage", C.c_int), ("tr_lvl", C.c_int),
+                ("update_ocn_f", C.c_int), ("hin_max", C.c_double * 6), ("hi_min", C.c_double)]
+
+
+THERM2_PTRS = ("aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "aicen_init", "vicen_init", "frain", "frzmlt", "Tf",
+               "rside", "tmask", "aice", "aice0", "fresh", "fsalt", "fhocn", "frazil", "meltl", "frz_onset")
+
+
+class Therm2Fields(C.Structure):
+    _fields_ = [("ncat", C.c_int), ("kitd", C.c_int), ("state_resident", C.c_int)] + [(n, C.c_void_p) for n in THERM2_PTRS]
+
+
 class ThermoFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in THERMO_STATE + THERMO_FORCING + THERMO_CAT_IN + THERMO_SW
                 + THERMO_OUT + THERMO_ONSET]
@@ -724,3 +738,81 @@ class Context:
             _f8(esnon), _f8(sst), _f8(Tf), _f8(strocnxT), _f8(strocnyT), _f8(Tbot), _f8(fbot),
             _f8(rside)))
         return Tbot, fbot, rside
+
+    # ---- thermodynamic changes of the thickness distribution (ice_therm_itd) -----
+    def itd_init(self, hin_max, ntrcr=1, trcr_depend=(0,), nt_Tsfc=1, nt_iage=0, nt_alvl=0, nt_vlvl=0, tr_iage=False,
+                 tr_lvl=False, update_ocn_f=True, hi_min=0.01):
+        """cice_itd_init: the module variables linear_itd / add_new_ice / lateral_melt read, after init_itd."""
+        cfg = ItdConfig()
+        cfg.ntrcr = ntrcr
+        for k, d in enumerate(trcr_depend):
+            cfg.trcr_depend[k] = d
+        cfg.nt_Tsfc, cfg.nt_iage, cfg.nt_alvl, cfg.nt_vlvl = nt_Tsfc, nt_iage, nt_alvl, nt_vlvl
+        cfg.tr_iage, cfg.tr_lvl, cfg.update_ocn_f = int(tr_iage), int(tr_lvl), int(update_ocn_f)
+        for k in range(NCAT + 1):
+            cfg.hin_max[k] = float(hin_max[k])
+        cfg.hi_min = hi_min
+        self._itd = (ntrcr, np.ascontiguousarray(trcr_depend, np.int32))
+        self._ck(self.lib.cice_itd_init(self.h, C.byref(cfg)))
+
+    def linear_itd(self, icells, indxi, indxj, a):
+        """cice_linear_itd on one block.  a: aicen_init, vicen_init, aicen, vicen, vsnon (ncat,ny,nx), trcrn (ncat,5,ny,nx),
+        eicen (ncat*nilyr,ny,nx), esnon (ncat*nslyr,ny,nx), aice, aice0 (ny,nx); updated in place.
+        Returns (l_stop, istop, jstop, cells not remapped)."""
+        ny, nx = a["aice"].shape
+        ntr, dep = self._itd
+        st = [C.c_int32(0) for _ in range(3)]
+        nn = C.c_longlong(0)
+        self._ck(self.lib.cice_linear_itd(
+            self.h, nx, ny, icells, _i4(indxi), _i4(indxj), ntr, _i4(dep),
+            *[_f8(a[k]) for k in ("aicen_init", "vicen_init", "aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "aice",
+                                  "aice0")], *[C.byref(x) for x in st], C.byref(nn)))
+        return st[0].value, st[1].value, st[2].value, nn.value
+
+    def add_new_ice(self, icells, indxi, indxj, dt, yday, a):
+        """cice_add_new_ice on one block.  a: tmask (int32), aicen, trcrn, vicen, eicen, aice0, aice, frzmlt, frazil,
+        frz_onset, fresh, fsalt, Tf; updated in place.  Returns (l_stop, istop, jstop)."""
+        ny, nx = a["aice"].shape
+        st = [C.c_int32(0) for _ in range(3)]
+        self._ck(self.lib.cice_add_new_ice(
+            self.h, nx, ny, self._itd[0], icells, _i4(indxi), _i4(indxj), _i4(a["tmask"]), C.c_double(dt),
+            *[_f8(a[k]) for k in ("aicen", "trcrn", "vicen", "eicen", "aice0", "aice", "frzmlt", "frazil", "frz_onset")],
+            C.c_double(yday), _f8(a["fresh"]), _f8(a["fsalt"]), _f8(a["Tf"]), *[C.byref(x) for x in st]))
+        return tuple(x.value for x in st)
+
+    def lateral_melt(self, ilo, ihi, jlo, jhi, dt, a):
+        """cice_lateral_melt on one block.  a: fresh, fsalt, fhocn, rside, meltl, aicen, vicen, vsnon, eicen, esnon."""
+        ny, nx = a["rside"].shape
+        self._ck(self.lib.cice_lateral_melt(
+            self.h, nx, ny, ilo, ihi, jlo, jhi, C.c_double(dt),
+            *[_f8(a[k]) for k in ("fresh", "fsalt", "fhocn", "rside", "meltl", "aicen", "vicen", "vsnon", "eicen", "esnon")]))
+
+    def shift_ice(self, icells, indxi, indxj, a):
+        """cice_shift_ice on one block.  a: aicen, trcrn, vicen, vsnon, eicen, esnon and hicen, donor (int32), daice, dvice
+        as (ncat, icells).  Returns (l_stop, istop, jstop)."""
+        ny, nx = a["aicen"].shape[-2:]
+        ntr, dep = self._itd
+        st = [C.c_int32(0) for _ in range(3)]
+        self._ck(self.lib.cice_shift_ice(
+            self.h, nx, ny, _i4(indxi), _i4(indxj), icells, ntr, _i4(dep),
+            *[_f8(a[k]) for k in ("aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "hicen")], _i4(a["donor"]),
+            _f8(a["daice"]), _f8(a["dvice"]), *[C.byref(x) for x in st]))
+        return tuple(x.value for x in st)
+
+    def step_therm2_itd(self, dt, yday, a, kitd=1, state_resident=False):
+        """cice_step_therm2_itd on the batch (thermo_batch_alloc).  a: the arrays of synth.therm2_state ((nb, ...));
+        aicen_init may be missing with a resident state.  Returns dict(l_stop, istop, jstop, bstop, stage)."""
+        f = Therm2Fields()
+        f.ncat, f.kitd, f.state_resident = NCAT, int(kitd), int(state_resident)
+        for n in THERM2_PTRS:
+            setattr(f, n, (_i4(a[n]) if n == "tmask" else _f8(a[n])) if n in a else None)
+        st = [C.c_int32(0) for _ in range(5)]
+        self._ck(self.lib.cice_step_therm2_itd(self.h, C.c_double(dt), C.c_double(yday), C.byref(f),
+                                               *[C.byref(x) for x in st]))
+        return dict(zip(("l_stop", "istop", "jstop", "bstop", "stage"), (x.value for x in st)))
+
+    def therm2_itd_times(self, enable=True):
+        """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""
+        ms = (C.c_float * 4)()
+        self._ck(self.lib.cice_therm2_itd_times(self.h, int(enable), ms))
+        return tuple(ms)

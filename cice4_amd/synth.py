@@ -389,3 +389,92 @@ def known_tsfc_inputs(a, solved, seed=20261003, perturb=0.3):
     b["flatn"] = solved["flatn"] * np.where(cold, rng.uniform(1.0 - perturb, 1.0 + perturb, shape), 1.0)
     b["trcrn"][0] = solved["trcrn"][0]
     return b
+
+
+# ----------------------------------------------------------------------------
+# block state after a thermodynamic step: input of step_therm2's first half
+# ----------------------------------------------------------------------------
+THERM2_STATE = ("aicen", "vicen", "vsnon", "trcrn", "eicen", "esnon")
+THERM2_2D = ("aice", "aice0", "frain", "frzmlt", "Tf", "rside", "fresh", "fsalt", "fhocn", "frazil", "meltl", "frz_onset")
+Tocnfrz = -1.8
+
+
+def therm2_state(regime="growth", nx=14, ny=12, nb=4, seed=20261018, ntrcr=1):
+    """Blocks (nb, ny, nx) with ghost cells as they stand between step_therm1 and step_therm2 (ice_step_mod.F90:286):
+    aicen_init / vicen_init from before the column physics, aicen / vicen / vsnon / eicen / esnon / trcrn after it (the
+    column physics changes thicknesses, not areas), and the 2-d fields the stage reads.  regime "growth": frzmlt > 0,
+    every category thickens; "melt": thinning, frzmlt < 0, rside > 0 under ice; "mixed": one or the other by cell.
+    Both hold: land, open water, empty categories, cells with ice in category 1 alone, ghost cells with ice and with
+    open ocean, cells whose cover leaves 1e-4 or nothing of open water, a category sitting 0.01 m from the boundary it
+    moves towards (it is emptied), cells nothing happened to (exactly representable tracers: they come back bit for
+    bit) and, under "growth", a few cells thickening by 3 m (linear_itd gives up on them: remap_flag false).
+    Tracers (ntrcr 1 or 4): Tsfc (depends on area), iage (volume), alvl (area), vlvl (volume)."""
+    assert regime in ("growth", "melt", "mixed") and ntrcr in (1, 4)
+    rng = np.random.default_rng(seed)
+    hm = hin_max()
+    top = hm.copy()
+    top[NCAT] = hm[NCAT - 1] + 2.0
+    shp = (nb, ny, nx)
+    ghost = np.ones(shp, bool)
+    ghost[:, 1:-1, 1:-1] = False
+    tmask = np.where(ghost, rng.random(shp) < 0.7, rng.random(shp) > 0.08)
+    grow = {"growth": np.ones(shp, bool), "melt": np.zeros(shp, bool), "mixed": rng.random(shp) < 0.5}[regime]
+    # what kind of cell: 0 open water, 1 ordinary, 2 category 1 alone, 3 brim (aice0 = 1e-4), 4 packed (no open water),
+    # 5 a category at the edge of its range, 6 quiet, 7 wild (growth only)
+    kind = rng.choice(8, size=shp, p=(0.14, 0.28, 0.12, 0.10, 0.10, 0.12, 0.10, 0.04))
+    kind[(kind == 7) & ~grow] = 1
+    kind[~tmask] = 0
+    ice = kind > 0
+    present = rng.random((nb, NCAT, ny, nx)) < 0.75
+    present[:, 0] |= ~present.any(axis=1)
+    present[:, 1:] &= (kind != 2)[:, None]
+    present[:, 0] |= kind == 2
+    frac = rng.uniform(0.05, 1.0, (nb, NCAT, ny, nx)) * present * ice[:, None]
+    tot = frac.sum(axis=1)
+    atot = rng.uniform(0.3, 0.95, shp)
+    atot[kind == 3] = 1.0 - 1.0e-4
+    atot[kind == 4] = 1.0 + 1.0e-9
+    aicen = frac / np.where(tot > 0, tot, 1.0)[:, None] * atot[:, None]
+    lo = np.array([top[n] + 0.15 * (top[n + 1] - top[n]) for n in range(NCAT)])
+    hi = np.array([top[n + 1] - 0.15 * (top[n + 1] - top[n]) for n in range(NCAT)])
+    u = rng.random((nb, NCAT, ny, nx))
+    hinit = lo[None, :, None, None] + u * (hi - lo)[None, :, None, None]
+    dh = rng.uniform(0.02, 0.12, (nb, NCAT, ny, nx)) * np.where(grow, 1.0, -1.0)[:, None]
+    edge_cat = rng.integers(0, NCAT - 1, shp)           # growth: category edge_cat to 0.01 below its upper boundary
+    for n in range(NCAT - 1):
+        m = (kind == 5) & (edge_cat == n)
+        mg, mm = m & grow, m & ~grow
+        hinit[:, n][mg] = hm[n + 1] - 0.01
+        hinit[:, n + 1][mm] = hm[n + 1] + 0.01          # melt: category edge_cat + 1 to 0.01 above its lower one
+        for k in (n, n + 1):
+            dh[:, k][mg] = 0.05
+            dh[:, k][mm] = -0.05
+    dh[np.broadcast_to((kind == 6)[:, None], dh.shape)] = 0.0
+    dh[np.broadcast_to((kind == 7)[:, None], dh.shape)] = 3.0
+    vicen_init = aicen * hinit
+    vicen = aicen * (hinit + dh)
+    snow = rng.random(shp) < 0.6
+    vsnon = aicen * rng.uniform(0.01, 0.3, aicen.shape) * snow[:, None]
+    qi = -rng.uniform(2.5e8, 3.3e8, (nb, NCAT, NILYR, ny, nx))
+    eicen = (qi * (vicen / NILYR)[:, :, None]).reshape(nb, NCAT * NILYR, ny, nx)
+    esnon = (-rng.uniform(1.0e8, 1.2e8, (nb, NCAT, NSLYR, ny, nx)) * (vsnon / NSLYR)[:, :, None]).reshape(nb, NCAT * NSLYR, ny, nx)
+    trcrn = np.zeros((nb, NCAT, 5, ny, nx))
+    has = aicen > 0
+    quiet = np.broadcast_to((kind == 6)[:, None], has.shape)
+    trcrn[:, :, 0] = np.where(has, np.where(quiet, -2.0, -rng.uniform(0.5, 20.0, has.shape)), Tocnfrz)
+    if ntrcr == 4:
+        trcrn[:, :, 1] = np.where(has, np.where(quiet, 1048576.0, rng.uniform(0.0, 1.0e7, has.shape)), 0.0)
+        trcrn[:, :, 2] = np.where(has, np.where(quiet, 0.5, rng.uniform(0.0, 1.0, has.shape)), 0.0)
+        trcrn[:, :, 3] = np.where(has, np.where(quiet, 0.25, rng.uniform(0.0, 1.0, has.shape)), 0.0)
+    aice = np.zeros(shp)
+    for n in range(NCAT):
+        aice = aice + aicen[:, n]
+    s = dict(aicen_init=aicen.copy(), vicen_init=vicen_init, aicen=aicen, vicen=vicen, vsnon=vsnon, trcrn=trcrn,
+             eicen=eicen, esnon=esnon, aice=aice, aice0=np.maximum(1.0 - aice, 0.0),
+             frain=rng.uniform(0.0, 1.0e-5, shp),
+             frzmlt=np.where(grow, rng.uniform(5.0, 80.0, shp), -rng.uniform(5.0, 200.0, shp)),
+             Tf=-1.8 + rng.uniform(-0.05, 0.05, shp),
+             rside=np.where(~grow & ice, rng.uniform(0.005, 0.05, shp), 0.0),
+             fresh=rng.uniform(0.0, 1.0e-5, shp), fsalt=rng.uniform(0.0, 1.0e-7, shp), fhocn=-rng.uniform(0.0, 5.0, shp),
+             frazil=np.zeros(shp), meltl=np.zeros(shp), frz_onset=np.zeros(shp), tmask=tmask.astype(np.int32))
+    return {k: np.ascontiguousarray(v) for k, v in s.items()}

@@ -506,6 +506,90 @@ int cice_frzmlt_bottom_lateral(cice_ctx *ctx, int nx_block, int ny_block, int il
                                const double *strocnyT, double *Tbot, double *fbot,
                                double *rside);
 
+/* ---- thermodynamic changes of the thickness distribution (source/ice_therm_itd.F90): the first half of step_therm2,
+ * source/ice_step_mod.F90:286-422 -- rain, aggregate_area, linear_itd, add_new_ice, lateral_melt -- on the device.
+ * cleanup_itd, bound_state, aggregate, ridging and shortwave stay with the caller.  No transcendental function on this
+ * path: results are those of the reference bit for bit (tests/test_gpu_therm_itd.py, tests/golden/therm_itd.npz; the
+ * "auscom" flavour compiles the same kernels with its own constants and has no parity fixture yet).
+ * cice_itd_init: call it after init_itd (source/ice_itd.F90:94) with the module variables the routines read:
+ * ntrcr, trcr_depend (ice_state), the tracer slots, tr_iage (ice_age), tr_lvl (ice_mechred), update_ocn_f (ice_flux),
+ * hin_max(0:ncat) and hi_min (ice_itd). */
+typedef struct {
+  int ntrcr;
+  int trcr_depend[CICE_MAX_NTRCR];
+  int nt_Tsfc, nt_iage, nt_alvl, nt_vlvl;  /* 1-based; 0 = absent */
+  int tr_iage, tr_lvl, update_ocn_f;
+  double hin_max[CICE_NCAT + 1];
+  double hi_min;
+} cice_itd_config;
+int cice_itd_init(cice_ctx *ctx, const cice_itd_config *cfg);
+
+/* Block-wise entries: host pointers, one (nx_block,ny_block) block, the reference's argument order; each call uploads,
+ * runs and downloads on its own.  trcrn is (nx,ny,max_ntrcr,ncat) as the host array lies (the first ntrcr planes are
+ * used), eicen (nx,ny,ncat*nilyr), esnon (nx,ny,ncat*nslyr).  indxi / indxj: 1-based, every cell at most once.
+ * A stop comes back as (l_stop, istop, jstop) with the cell the reference would name and the arrays as the reference
+ * leaves them at that point.
+ * linear_itd (ice_therm_itd.F90:58-705; inside it hin_max(ncat) = 999.9).  *n_not_remapped: cells whose remap_flag
+ * went false (the reference prints their diagnosis, :324-379); they keep their areas and volumes. */
+int cice_linear_itd(cice_ctx *ctx, int nx_block, int ny_block, int icells, const int32_t *indxi, const int32_t *indxj,
+                    int ntrcr, const int32_t *trcr_depend, const double *aicen_init, const double *vicen_init,
+                    double *aicen, double *trcrn, double *vicen, double *vsnon, double *eicen, double *esnon,
+                    double *aice, double *aice0, int32_t *l_stop, int32_t *istop, int32_t *jstop,
+                    long long *n_not_remapped);
+/* add_new_ice (ice_therm_itd.F90:843-1247); tmask is passed through as in the reference, the list decides the cells.
+ * A failed volume check (:1238-1245) names the last failing cell of the list; the arrays are fully updated then. */
+int cice_add_new_ice(cice_ctx *ctx, int nx_block, int ny_block, int ntrcr, int icells, const int32_t *indxi,
+                     const int32_t *indxj, const int32_t *tmask, double dt, double *aicen, double *trcrn, double *vicen,
+                     double *eicen, double *aice0, const double *aice, const double *frzmlt, double *frazil,
+                     double *frz_onset, double yday, double *fresh, double *fsalt, const double *Tf, int32_t *l_stop,
+                     int32_t *istop, int32_t *jstop);
+/* lateral_melt (ice_therm_itd.F90:1266-1420) */
+int cice_lateral_melt(cice_ctx *ctx, int nx_block, int ny_block, int ilo, int ihi, int jlo, int jhi, double dt,
+                      double *fresh, double *fsalt, double *fhocn, const double *rside, double *meltl, double *aicen,
+                      double *vicen, double *vsnon, double *eicen, double *esnon);
+/* shift_ice (source/ice_itd.F90:892-1340); hicen, donor, daice, dvice are (icells, ncat).  donor(ij, n) must be 0, n or
+ * n + 1, and not 0 where daice(ij, n) > 0 (the reference would index category 0): CICE_EINVAL otherwise.
+ * Stop rule: the first boundary n with a failing cell; there the kinds in the order negative daice, negative dvice,
+ * daice > aicen, dvice > vicen; of the matching cells the LAST in list order.  Transfers across earlier boundaries
+ * are kept, the tracers are not recomputed.  The "negative" kinds follow the reference's text, in which the donor
+ * category of the message loops is stale (:1101-1141); no fixture pins them. */
+int cice_shift_ice(cice_ctx *ctx, int nx_block, int ny_block, const int32_t *indxi, const int32_t *indxj, int icells,
+                   int ntrcr, const int32_t *trcr_depend, double *aicen, double *trcrn, double *vicen, double *vsnon,
+                   double *eicen, double *esnon, double *hicen, const int32_t *donor, double *daice, double *dvice,
+                   int32_t *l_stop, int32_t *istop, int32_t *jstop);
+
+/* The stage as ONE call on the batch of cice_thermo_batch_alloc, all blocks (ice_step_mod.F90:286-422): 1 rain drain
+ * (fresh += frain*aice), 2 aggregate_area, 3 linear_itd (blocks with a cell aice > puny), 4 add_new_ice (every tmask
+ * cell of the whole block, ghost cells included), 5 lateral_melt.  kitd = 0 leaves 2 and 3 out.
+ * Field shapes as in cice_thermo_fields; 2-d fields (nx,ny,nb).
+ * state_resident = 1: aicen, vicen, vsnon, eicen, esnon and the surface-temperature plane of trcrn are taken from the
+ *   device copies cice_step_therm1 / _abl left (the host arrays must be what that call downloaded: they are the
+ *   download targets, and the source from which a stopping call restores its inputs); uploaded are the other tracer
+ *   planes, vicen_init, aicen_init where non-NULL (NULL: the copy the batch kept; CICE_EINVAL if no cice_step_therm1
+ *   call on this batch has made one), and the 2-d fields.
+ * state_resident = 0: the state is uploaded too (aicen_init is required).
+ * aice is read (the rain term and, with kitd = 0, add_new_ice use the caller's) and written; aice0 is read with
+ * kitd = 0; meltl is read and added to; frazil is written.
+ * One download: the state with the ntrcr tracer planes, aice, aice0, fresh, fsalt, fhocn, frazil, meltl, frz_onset.
+ * Stops: *stage = 1 linear_itd, 2 add_new_ice (3 is reserved for lateral_melt, which cannot stop), *bstop the block
+ * (1-based), (istop, jstop) the cell.  The failing block holds what the reference's arrays hold at its abort_ice; the
+ * blocks in front of it have completed the stage, the blocks behind it come back as they went in (rain included).
+ * ncat must be CICE_NCAT; ncat = 1 is CICE_EUNSUPPORTED (its reduce_area branch, ice_step_mod.F90:430, is not built). */
+typedef struct {
+  int ncat, kitd, state_resident;
+  double *aicen, *trcrn, *vicen, *vsnon, *eicen, *esnon;
+  const double *aicen_init, *vicen_init;
+  const double *frain, *frzmlt, *Tf, *rside;
+  const int32_t *tmask;
+  double *aice, *aice0, *fresh, *fsalt, *fhocn, *frazil, *meltl, *frz_onset;
+} cice_therm2_fields;
+int cice_step_therm2_itd(cice_ctx *ctx, double dt, double yday, const cice_therm2_fields *f, int32_t *l_stop,
+                         int32_t *istop, int32_t *jstop, int32_t *bstop, int32_t *stage);
+/* Measurement aid (scripts/therm2_itd_cost.py), off by default: enable != 0 makes the following cice_step_therm2_itd
+ * calls record HIP events around their kernels; ms (may be NULL) receives the device times (ms) of the last call that
+ * did: rain + aggregate_area, linear_itd, add_new_ice, lateral_melt. */
+int cice_therm2_itd_times(cice_ctx *ctx, int enable, float ms[4]);
+
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
  * dependencies from ntrcr / trcr_depend (ice_init.F90:848-852: 0 area tracer, 1 ice-volume, 2 snow-volume tracer),
