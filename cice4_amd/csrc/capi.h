@@ -1,0 +1,164 @@
+// Private to the C-ABI glue (capi*.hip): the context behind the opaque cice_ctx of include/cice4_amd.h, the frame every
+// entry is wrapped in, and the few helpers more than one of those units needs.
+#pragma once
+#include <rccl/rccl.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <algorithm>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "common.h"
+#include "domain.h"
+#include "evp.h"
+#include "halo.h"
+#include "atmo.h"
+#include "therm.h"
+#include "itd.h"
+#include "transport.h"
+
+using namespace cice;
+
+// Page-locked host buffer of an entry that is called again and again with the same size: grown only when a larger
+// request comes along, then by half as much again; freed by cice_destroy.
+struct HostBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  void* need(size_t want) {
+    if (bytes < want) {
+      release();
+      CICE_HIP(hipHostMalloc(&p, want + want / 2, hipHostMallocDefault));
+      bytes = want + want / 2;
+    }
+    return p;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+struct cice_ctx {
+  int device = -1;
+  hipStream_t stream = nullptr;
+  std::string err;
+  Domain dom;
+  bool have_domain = false;
+  std::unique_ptr<Halo> halo;
+  std::unique_ptr<Evp> evp;
+  std::unique_ptr<Transport> transport;
+  std::unique_ptr<Upwind> upwind;
+  // RCCL communicator of this rank (cice_comm_init): created once, handed to every Halo built afterwards --
+  // the block decomposition may change (cice_domain_create*), the set of ranks does not
+  ncclComm_t comm = nullptr;
+  int comm_rank = -1, comm_nranks = 0;
+  CopyFan fan;                 // side streams for the entries that move many separate host arrays: ONE set per context,
+                               // shared by the dynamics, the thermodynamic half-step and the transport
+  hipStream_t cs() { return fan.forked ? fan.next() : stream; }   // the stream for the next host <-> device copy
+  // evp -> transport chain (cice_transport_chain): the host arrays the transport calls will be given; chain_ready: a
+  // cice_evp call has prefetched them and no transport call has consumed that yet
+  cice_transport_fields chain{};
+  bool chain_on = false, chain_ready = false;
+  const double *chain_aicen = nullptr, *chain_vicen = nullptr, *chain_u = nullptr, *chain_v = nullptr;   // what cice_evp was given
+  double chio = 0.006;         // coupled flavour: the namelist's chio (cice_thermo_set_chio)
+  double nml[4] = {1.0, 0.0, 0.00536, 0.0};   // coupled flavour: cosw, sinw, dragio, use_ocnslope last sent to the device
+  bool nml_set = false;
+  LocalLink* link = nullptr;   // stand-in for the communicator without RCCL (cice_comm_init_local / _shm; tests)
+  bool link_owned = false;     // the shared-memory form belongs to this context
+  // Page-locked host ranges of this context: [start, end) in bytes, disjoint.  One manager for the explicit
+  // registrations (cice_host_register, cice_evp_pin_fields): a new range that touches registered ones is registered
+  // as their union (a whole array after some of its slices), because a copy whose host range is partly registered
+  // is refused by the runtime.  CICE4_AMD_PIN=0 in the environment leaves everything pageable (diagnostic).
+  // Exact byte ranges, not page-rounded, for the same reason (a neighbouring variable sharing the last page).
+  std::vector<std::pair<uintptr_t, uintptr_t>> pin_ranges;
+  std::vector<std::pair<uintptr_t, uintptr_t>> pin_refused;  // ranges hipHostRegister turned down (not retried)
+  void pin_range(const void* p, size_t bytes);
+  void unpin_all();
+  // staging of the host-pointer entries (thermo_vertical is called ncat x nblocks times per step with
+  // the same block size: allocated once, grown only when a larger block comes along)
+  DevBuf<double> tv_stage, fz_stage, halo_stage;
+  // page-locked gather buffer and cell offsets of the compact thermo_vertical path
+  HostBuf tv_host;
+  std::vector<size_t> tv_cells;
+  // frame of the rank's blocks (cells a halo update can read or write), for host-array halo updates
+  std::vector<int32_t> frame;
+  std::vector<size_t> frame_at;
+  std::unique_ptr<Halo> frame_halo;   // the domain's lists re-addressed to positions in the gathered frame
+  DevBuf<double> frame_pack;
+  HostBuf frame_host;
+  DevBuf<int32_t> tv_list;
+  // thermo
+  ThermoParams tp{};
+  bool have_thermo = false;
+  DevBuf<unsigned long long> tkey;  // THERMO_STATUS_WORDS: [0] error key, then the update counters (therm.h)
+  // batched thermo state
+  struct Batch {
+    int nx = 0, ny = 0, nb = 0;
+    DevBuf<int32_t> blk;
+    DevBuf<double> aicen, trcrn, vicen, vsnon, eicen, esnon, flw, potT, Qa, rhoa, fsnow, fbot, Tbot,
+        lhcoef, shcoef, fswsfc, fswint, fswthrun, Sswabs, Iswabs, out15, mlt_onset, frz_onset;
+    DevBuf<double> mrg_in, mrg_acc, fz_in;   // merge_fluxes inputs / accumulators, frzmlt inputs + rside
+    DevBuf<int32_t> perm;                    // columns of every chunk sorted by expected work (k_thermo_sort)
+    int sort_chunk = 0, sort_group = 8;      // chunk 0: no sorting (k_thermo_dense) -- the default: DESIGN.md 3.3
+    DevBuf<unsigned char> niter;             // solver iterations of every (cell, category) in the last step
+    DevBuf<double> atm_in;                   // uatm, vatm, wind, zlvl, strax, stray (cice_step_therm1_abl)
+    std::vector<int32_t> hblk;               // ilo, ihi, jlo, jhi per block (host copy of blk)
+    bool kept_aicen_init = false;            // mrg_in holds the concentrations cice_step_therm1 found (cice_step_therm2_itd)
+  } tb;
+  // thickness-distribution stage (itd.h): module variables given to cice_itd_init, staging of the block-wise entries
+  // (grown on demand), the batch's extra fields, record words, the events of cice_therm2_itd_times
+  ItdParams ip{};
+  bool have_itd = false;
+  DevBuf<double> itd_d, itd_b;
+  DevBuf<int32_t> itd_i, itd_bi;
+  DevBuf<unsigned long long> itd_rec;
+  hipEvent_t itd_ev[5] = {};
+  bool itd_timed = false;                  // cice_therm2_itd_times(enable): events around the stage's kernels
+  float itd_ms[4] = {0, 0, 0, 0};
+  // device is required lazily: domain queries work on a CPU-only host
+  // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
+  // process may have changed the current device since the last call (another context on another GPU,
+  // torch.cuda.set_device, another thread).
+  void bind_device() {
+    if (stream) CICE_HIP(hipSetDevice(device));
+  }
+  void need_device();
+  void need_halo();
+  void connect(Halo& h);       // hands this rank's communicator or link, if any, to a Halo built on the domain
+};
+
+#define CICE_TRY_QUEUED(ctx_) \
+  cice_ctx* c_ = (ctx_); \
+  if (!c_) return CICE_EINVAL; \
+  try {                        \
+    c_->bind_device();         \
+    c_->fan.forked = false;   /* an entry that failed between fork and join leaves nothing behind for the next */
+// Every entry but the two that may leave one-launch EVP loops pending (cice_evp_subcycles, and cice_evp_get_info asked for
+// "resident_pending") first looks at the records of the pending ones (Evp::retire_resident): whatever it reads, launches or
+// changes then finds the state a wait behind every loop would have left.
+#define CICE_TRY(ctx_)  \
+  CICE_TRY_QUEUED(ctx_) \
+    if (c_->evp) c_->evp->retire_resident();
+#define CICE_CATCH                                            \
+  }                                                           \
+  catch (const Error& e) {                                    \
+    c_->err = e.msg;                                          \
+    return e.code;                                            \
+  }                                                           \
+  catch (const std::exception& e) {                           \
+    c_->err = e.what();                                       \
+    return CICE_EINVAL;                                       \
+  }                                                           \
+  return CICE_OK;
+
+// "no stop": what every entry with the reference's l_stop / istop / jstop reports first
+inline void clear_stop(int32_t* l_stop, int32_t* istop, int32_t* jstop) { *l_stop = 0; *istop = 0; *jstop = 0; }
+
+// Plane `it` of trcrn(nx, ny, max_ntrcr, ncat, nblocks) for every (category, block) of the thermodynamic batch, one strided
+// copy between the caller's array and the batch's (capi_thermo.hip); `from` and `to` are the two arrays' first elements
+void batch_tracer_copy(cice_ctx* c, int it, const double* from, double* to, hipMemcpyKind kind);

@@ -1,0 +1,407 @@
+// C-ABI of libcice4_amd.so: thermodynamic changes of the thickness distribution, block-wise and on the batch.
+#include "capi.h"
+
+namespace {
+// plane offsets of the block-wise staging buffer (units of nx*ny doubles)
+enum { IB_AICEN = 0, IB_VICEN = 5, IB_VSNON = 10, IB_TRCRN = 15, IB_EICEN = 40, IB_ESNON = 60, IB_AINIT = 65,
+       IB_VINIT = 70, IB_2D = 75, IB_SHIFT = 87, IB_PLANES = 102 };
+enum { I2_AICE = 0, I2_AICE0, I2_FRAIN, I2_FRZMLT, I2_TF, I2_RSIDE, I2_FRESH, I2_FSALT, I2_FHOCN, I2_FRAZIL, I2_MELTL,
+       I2_FRZ_ONSET };
+static_assert(NCAT == 5 && NILYR == 4 && NSLYR == 1 && NTRCR == 5, "plane offsets above");
+
+// the record words once the stream has run dry
+void itd_read_rec(cice_ctx* c, unsigned long long h[ITD_REC_WORDS]) {
+  CICE_HIP(hipMemcpyAsync(h, c->itd_rec.p, ITD_REC_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+  CICE_HIP(hipStreamSynchronize(c->stream));
+}
+
+// the state arrays of the block-wise entries in the order they travel; an entry moves the members it names
+enum { ST_AICEN = 1, ST_VICEN = 2, ST_VSNON = 4, ST_TRCRN = 8, ST_EICEN = 16, ST_ESNON = 32, ST_ALL = 63 };
+struct ItdState { double *aicen, *vicen, *vsnon, *trcrn, *eicen, *esnon; };
+
+// the list key of the cell shift_ice names after a limited launch at boundary N (itd.h: STOPS)
+unsigned long long itd_shift_key(const unsigned long long* r, int N) {
+  const int stale = (int)(r[ITD_REC_LASTDONOR] & 7) - N;   // 0 / 1: the donor of the last cell with donor > 0 is N / N + 1
+  for (int k = 0; k < 4; ++k) {
+    if (!r[ITD_REC_FLAG + k]) continue;
+    unsigned long long key = 0;
+    if (k < 2 && (stale == 0 || stale == 1)) key = r[(k == 0 ? ITD_REC_NEG_DA : ITD_REC_NEG_DV) + stale];
+    if (k == 2) key = r[ITD_REC_GT_DA];
+    if (k == 3) key = r[ITD_REC_GT_DV];
+    if (key) return key;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (r[ITD_REC_FLAG + k]) return r[ITD_REC_FLAG + k];
+  return 0;
+}
+
+struct ItdBlock {   // one (nx, ny) block staged on the device
+  cice_ctx* c;
+  size_t np;
+  ItdArgs a{};
+  std::vector<int32_t> lp;
+  const int32_t *indxi, *indxj;
+  double* pl(int plane) const { return c->itd_d.p + (size_t)plane * np; }
+  ItdBlock(cice_ctx* c_, int nx, int ny, int icells, const int32_t* indxi_, const int32_t* indxj_)
+      : c(c_), np((size_t)nx * ny), indxi(indxi_), indxj(indxj_) {
+    CICE_REQUIRE(c->have_itd, "cice_itd_init has not been called");
+    CICE_REQUIRE(nx >= 1 && ny >= 1 && icells >= 0 && (size_t)icells <= np && (icells == 0 || (indxi && indxj)),
+                 "bad dimensions or NULL index list");
+    lp.assign(np, 0);
+    for (int ij = 0; ij < icells; ++ij) {
+      CICE_REQUIRE(indxi[ij] >= 1 && indxi[ij] <= nx && indxj[ij] >= 1 && indxj[ij] <= ny, "index list outside the block");
+      int32_t& w = lp[(size_t)(indxj[ij] - 1) * nx + indxi[ij] - 1];
+      CICE_REQUIRE(w == 0, "index list names a cell twice");
+      w = ij + 1;
+    }
+    c->need_device();
+    if (c->itd_d.n < IB_PLANES * np) c->itd_d.alloc(IB_PLANES * np);
+    if (c->itd_i.n < 7 * np + 4) c->itd_i.alloc(7 * np + 4);
+    c->itd_rec.alloc(ITD_REC_WORDS);
+    const int32_t blk[4] = {1, nx, 1, ny};
+    hipStream_t s = c->stream;
+    CICE_HIP(hipMemcpyAsync(c->itd_i.p, lp.data(), np * 4, hipMemcpyHostToDevice, s));
+    CICE_HIP(hipMemcpyAsync(c->itd_i.p + 7 * np, blk, 16, hipMemcpyHostToDevice, s));
+    CICE_HIP(hipStreamSynchronize(s));   // blk is a local
+    a.p = c->ip;
+    a.nx = nx; a.ny = ny; a.nblocks = 1; a.icells = icells; a.kitd = 1; a.bfail = 1; a.nlimit = 0; a.bend = 1;
+    a.listpos = c->itd_i.p; a.blk = c->itd_i.p + 7 * np;
+    a.aicen = pl(IB_AICEN); a.vicen = pl(IB_VICEN); a.vsnon = pl(IB_VSNON); a.trcrn = pl(IB_TRCRN);
+    a.eicen = pl(IB_EICEN); a.esnon = pl(IB_ESNON); a.aicen_init = pl(IB_AINIT); a.vicen_init = pl(IB_VINIT);
+    a.aice = pl(IB_2D + I2_AICE); a.aice0 = pl(IB_2D + I2_AICE0); a.frzmlt = pl(IB_2D + I2_FRZMLT);
+    a.Tf = pl(IB_2D + I2_TF); a.rside = pl(IB_2D + I2_RSIDE); a.fresh = pl(IB_2D + I2_FRESH);
+    a.fsalt = pl(IB_2D + I2_FSALT); a.fhocn = pl(IB_2D + I2_FHOCN); a.frazil = pl(IB_2D + I2_FRAZIL);
+    a.meltl = pl(IB_2D + I2_MELTL); a.frz_onset = pl(IB_2D + I2_FRZ_ONSET);
+    a.rec = c->itd_rec.p;
+  }
+  void set_tracers(int ntrcr, const int32_t* dep) {   // the reference passes ntrcr, trcr_depend with every call
+    CICE_REQUIRE(ntrcr >= 1 && ntrcr <= NTRCR && a.p.it_Tsfc < ntrcr, "ntrcr out of range");
+    a.p.ntrcr = ntrcr;
+    for (int k = 0; k < ntrcr && dep; ++k) {
+      CICE_REQUIRE(dep[k] >= 0 && dep[k] <= 2, "trcr_depend must be 0, 1 or 2");
+      a.p.dep[k] = dep[k];
+    }
+  }
+  void up(int plane, const double* h, int planes = 1) const {
+    CICE_HIP(hipMemcpyAsync(pl(plane), h, (size_t)planes * np * 8, hipMemcpyHostToDevice, c->stream));
+  }
+  void down(double* h, int plane, int planes = 1) const {
+    CICE_HIP(hipMemcpyAsync(h, pl(plane), (size_t)planes * np * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  void state(const ItdState& h, int members, bool to_device) const {
+    const struct { int member, plane, planes; double* h; } list[] = {
+        {ST_AICEN, IB_AICEN, NCAT, h.aicen}, {ST_VICEN, IB_VICEN, NCAT, h.vicen}, {ST_VSNON, IB_VSNON, NCAT, h.vsnon},
+        {ST_TRCRN, IB_TRCRN, NCAT * NTRCR, h.trcrn}, {ST_EICEN, IB_EICEN, NCAT * NILYR, h.eicen},
+        {ST_ESNON, IB_ESNON, NCAT * NSLYR, h.esnon}};
+    for (const auto& x : list)
+      if (members & x.member) to_device ? up(x.plane, x.h, x.planes) : down(x.h, x.plane, x.planes);
+  }
+  void clear_rec() const { CICE_HIP(hipMemsetAsync(c->itd_rec.p, 0, ITD_REC_WORDS * 8, c->stream)); }
+  // shift_ice stopped (r[ITD_REC_SHIFT]): again from the inputs, up to the failing boundary (itd.h), for the cell to name
+  template <class Upload, class Launch>
+  void rerun_to_stop(unsigned long long r[ITD_REC_WORDS], Upload upload, Launch launch, int32_t* l_stop, int32_t* istop,
+                     int32_t* jstop) {
+    const int N = NCAT - (int)((r[ITD_REC_SHIFT] - 1) & 0xff);
+    upload();
+    clear_rec();
+    a.bfail = 0; a.nlimit = N;         // (bfail: linear_itd's kernel; shift_ice's own does not read it)
+    launch();
+    itd_read_rec(c, r);
+    const unsigned long long key = itd_shift_key(r, N);
+    *l_stop = 1;
+    if (key) { *istop = indxi[key - 1]; *jstop = indxj[key - 1]; }
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int cice_itd_init(cice_ctx* ctx, const cice_itd_config* cfg) {
+  CICE_TRY(ctx)
+  CICE_REQUIRE(cfg, "NULL argument");
+  CICE_REQUIRE(cfg->ntrcr >= 1 && cfg->ntrcr <= NTRCR, "cice_itd_init: ntrcr out of range");
+  ItdParams p{};
+  p.ntrcr = cfg->ntrcr;
+  for (int k = 0; k < cfg->ntrcr; ++k) {
+    CICE_REQUIRE(cfg->trcr_depend[k] >= 0 && cfg->trcr_depend[k] <= 2, "cice_itd_init: trcr_depend must be 0, 1 or 2");
+    p.dep[k] = cfg->trcr_depend[k];
+  }
+  auto slot = [&](int nt, bool needed, const char* what) {
+    CICE_REQUIRE(!needed || (nt >= 1 && nt <= cfg->ntrcr), what);
+    return nt - 1;
+  };
+  p.it_Tsfc = slot(cfg->nt_Tsfc, true, "cice_itd_init: nt_Tsfc is not a tracer in use");
+  p.it_iage = slot(cfg->nt_iage, cfg->tr_iage != 0, "cice_itd_init: tr_iage without nt_iage");
+  p.it_alvl = slot(cfg->nt_alvl, cfg->tr_lvl != 0, "cice_itd_init: tr_lvl without nt_alvl");
+  p.it_vlvl = slot(cfg->nt_vlvl, cfg->tr_lvl != 0, "cice_itd_init: tr_lvl without nt_vlvl");
+  p.tr_iage = cfg->tr_iage != 0; p.tr_lvl = cfg->tr_lvl != 0; p.update_ocn_f = cfg->update_ocn_f != 0;
+  for (int n = 0; n <= NCAT; ++n) p.hin_max[n] = cfg->hin_max[n];
+  p.hi_min = cfg->hi_min;
+  c_->ip = p;
+  c_->have_itd = true;
+  CICE_CATCH
+}
+
+int cice_linear_itd(cice_ctx* ctx, int nx, int ny, int icells, const int32_t* indxi, const int32_t* indxj, int ntrcr,
+                    const int32_t* trcr_depend, const double* aicen_init, const double* vicen_init, double* aicen,
+                    double* trcrn, double* vicen, double* vsnon, double* eicen, double* esnon, double* aice,
+                    double* aice0, int32_t* l_stop, int32_t* istop, int32_t* jstop, long long* n_not_remapped) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(aicen_init && vicen_init && aicen && trcrn && vicen && vsnon && eicen && esnon && aice && aice0 && l_stop &&
+                   istop && jstop, "linear_itd: NULL argument");
+  ItdBlock B(c_, nx, ny, icells, indxi, indxj);
+  B.set_tracers(ntrcr, trcr_depend);
+  const ItdState st{aicen, vicen, vsnon, trcrn, eicen, esnon};
+  auto up_state = [&] {
+    B.state(st, ST_ALL, true);
+    B.up(IB_2D + I2_AICE, aice); B.up(IB_2D + I2_AICE0, aice0);
+  };
+  auto launch = [&] { itd_launch_linear(B.a, c_->stream); };
+  up_state();
+  B.up(IB_AINIT, aicen_init, NCAT); B.up(IB_VINIT, vicen_init, NCAT);
+  B.clear_rec();
+  launch();
+  unsigned long long r[ITD_REC_WORDS];
+  itd_read_rec(c_, r);
+  clear_stop(l_stop, istop, jstop);
+  if (n_not_remapped) *n_not_remapped = (long long)r[ITD_REC_NOREMAP];
+  if (r[ITD_REC_SHIFT]) B.rerun_to_stop(r, up_state, launch, l_stop, istop, jstop);
+  B.state(st, ST_ALL, false);
+  B.down(aice, IB_2D + I2_AICE); B.down(aice0, IB_2D + I2_AICE0);
+  CICE_HIP(hipStreamSynchronize(c_->stream));
+  CICE_CATCH
+}
+
+int cice_shift_ice(cice_ctx* ctx, int nx, int ny, const int32_t* indxi, const int32_t* indxj, int icells, int ntrcr,
+                   const int32_t* trcr_depend, double* aicen, double* trcrn, double* vicen, double* vsnon, double* eicen,
+                   double* esnon, double* hicen, const int32_t* donor, double* daice, double* dvice, int32_t* l_stop,
+                   int32_t* istop, int32_t* jstop) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(aicen && trcrn && vicen && vsnon && eicen && esnon && hicen && donor && daice && dvice && l_stop && istop &&
+                   jstop, "shift_ice: NULL argument");
+  for (int n = 1; n < NCAT; ++n)
+    for (int ij = 0; ij < icells; ++ij) {
+      const int d = donor[(size_t)(n - 1) * icells + ij];
+      CICE_REQUIRE(d == 0 || d == n || d == n + 1, "shift_ice: donor(ij, n) must be 0, n or n + 1");
+      CICE_REQUIRE(d != 0 || !(daice[(size_t)(n - 1) * icells + ij] > 0.0), "shift_ice: daice > 0 without a donor");
+    }
+  ItdBlock B(c_, nx, ny, icells, indxi, indxj);
+  B.set_tracers(ntrcr, trcr_depend);
+  const size_t np = B.np, ne = (size_t)icells * NCAT;
+  double* dsh = B.pl(IB_SHIFT);        // hicen, daice, dvice: 3 x icells x ncat <= 15 planes
+  int32_t* ddon = c_->itd_i.p + np;    // donor: icells x ncat <= 5 planes
+  B.a.hicen = dsh; B.a.daice = dsh + ne; B.a.dvice = dsh + 2 * ne; B.a.donor = ddon;
+  hipStream_t s = c_->stream;
+  const ItdState st{aicen, vicen, vsnon, trcrn, eicen, esnon};
+  auto up_state = [&] {
+    B.state(st, ST_ALL, true);
+    if (ne) {
+      CICE_HIP(hipMemcpyAsync(dsh, hicen, ne * 8, hipMemcpyHostToDevice, s));
+      CICE_HIP(hipMemcpyAsync(dsh + ne, daice, ne * 8, hipMemcpyHostToDevice, s));
+      CICE_HIP(hipMemcpyAsync(dsh + 2 * ne, dvice, ne * 8, hipMemcpyHostToDevice, s));
+      CICE_HIP(hipMemcpyAsync(ddon, donor, ne * 4, hipMemcpyHostToDevice, s));
+    }
+  };
+  auto launch = [&] { itd_launch_shift(B.a, s); };
+  up_state();
+  B.clear_rec();
+  launch();
+  unsigned long long r[ITD_REC_WORDS];
+  itd_read_rec(c_, r);
+  clear_stop(l_stop, istop, jstop);
+  if (r[ITD_REC_SHIFT]) B.rerun_to_stop(r, up_state, launch, l_stop, istop, jstop);
+  B.state(st, ST_ALL, false);
+  if (ne) {
+    CICE_HIP(hipMemcpyAsync(hicen, dsh, ne * 8, hipMemcpyDeviceToHost, s));
+    CICE_HIP(hipMemcpyAsync(daice, dsh + ne, ne * 8, hipMemcpyDeviceToHost, s));
+    CICE_HIP(hipMemcpyAsync(dvice, dsh + 2 * ne, ne * 8, hipMemcpyDeviceToHost, s));
+  }
+  CICE_HIP(hipStreamSynchronize(s));
+  CICE_CATCH
+}
+
+int cice_add_new_ice(cice_ctx* ctx, int nx, int ny, int ntrcr, int icells, const int32_t* indxi, const int32_t* indxj,
+                     const int32_t* tmask, double dt, double* aicen, double* trcrn, double* vicen, double* eicen,
+                     double* aice0, const double* aice, const double* frzmlt, double* frazil, double* frz_onset,
+                     double yday, double* fresh, double* fsalt, const double* Tf, int32_t* l_stop, int32_t* istop,
+                     int32_t* jstop) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  (void)tmask;                         // the reference does not read it either
+  CICE_REQUIRE(aicen && trcrn && vicen && eicen && aice0 && aice && frzmlt && frazil && fresh && fsalt && Tf && l_stop &&
+                   istop && jstop, "add_new_ice: NULL argument");
+  CICE_REQUIRE(dt > 0.0, "add_new_ice: dt");
+  ItdBlock B(c_, nx, ny, icells, indxi, indxj);
+  B.set_tracers(ntrcr, nullptr);
+  B.a.dt = dt; B.a.yday = yday;
+  if (!frz_onset) B.a.frz_onset = nullptr;   // `present(frz_onset)`, :1041
+  const ItdState st{aicen, vicen, nullptr, trcrn, eicen, nullptr};
+  const int members = ST_AICEN | ST_VICEN | ST_TRCRN | ST_EICEN;
+  B.state(st, members, true);
+  B.up(IB_2D + I2_AICE, aice); B.up(IB_2D + I2_AICE0, aice0); B.up(IB_2D + I2_FRZMLT, frzmlt);
+  B.up(IB_2D + I2_TF, Tf); B.up(IB_2D + I2_FRAZIL, frazil); B.up(IB_2D + I2_FRESH, fresh); B.up(IB_2D + I2_FSALT, fsalt);
+  if (frz_onset) B.up(IB_2D + I2_FRZ_ONSET, frz_onset);
+  B.clear_rec();
+  itd_launch_add_new_ice(B.a, c_->stream);
+  B.state(st, members, false);
+  B.down(aice0, IB_2D + I2_AICE0); B.down(frazil, IB_2D + I2_FRAZIL); B.down(fresh, IB_2D + I2_FRESH);
+  B.down(fsalt, IB_2D + I2_FSALT);
+  if (frz_onset) B.down(frz_onset, IB_2D + I2_FRZ_ONSET);
+  unsigned long long r[ITD_REC_WORDS];
+  itd_read_rec(c_, r);
+  clear_stop(l_stop, istop, jstop);
+  if (r[ITD_REC_ADD]) {
+    const unsigned long long key = r[ITD_REC_ADD] & 0xffffffffull;
+    *l_stop = 1; *istop = indxi[key - 1]; *jstop = indxj[key - 1];
+  }
+  CICE_CATCH
+}
+
+int cice_lateral_melt(cice_ctx* ctx, int nx, int ny, int ilo, int ihi, int jlo, int jhi, double dt, double* fresh,
+                      double* fsalt, double* fhocn, const double* rside, double* meltl, double* aicen, double* vicen,
+                      double* vsnon, double* eicen, double* esnon) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(fresh && fsalt && fhocn && rside && meltl && aicen && vicen && vsnon && eicen && esnon,
+               "lateral_melt: NULL argument");
+  CICE_REQUIRE(nx >= 1 && ny >= 1 && ilo >= 1 && ihi <= nx && jlo >= 1 && jhi <= ny && dt > 0.0, "bad dimensions");
+  ItdBlock B(c_, nx, ny, 0, nullptr, nullptr);
+  B.a.dt = dt;
+  const int32_t blk[4] = {ilo, ihi, jlo, jhi};
+  CICE_HIP(hipMemcpyAsync(c_->itd_i.p + 7 * B.np, blk, 16, hipMemcpyHostToDevice, c_->stream));
+  CICE_HIP(hipStreamSynchronize(c_->stream));
+  const ItdState st{aicen, vicen, vsnon, nullptr, eicen, esnon};
+  B.state(st, ST_ALL & ~ST_TRCRN, true);
+  B.up(IB_2D + I2_RSIDE, rside); B.up(IB_2D + I2_FRESH, fresh); B.up(IB_2D + I2_FSALT, fsalt);
+  B.up(IB_2D + I2_FHOCN, fhocn); B.up(IB_2D + I2_MELTL, meltl);
+  itd_launch_lateral_melt(B.a, c_->stream);
+  B.state(st, ST_ALL & ~ST_TRCRN, false);
+  B.down(fresh, IB_2D + I2_FRESH); B.down(fsalt, IB_2D + I2_FSALT); B.down(fhocn, IB_2D + I2_FHOCN);
+  B.down(meltl, IB_2D + I2_MELTL);
+  CICE_HIP(hipStreamSynchronize(c_->stream));
+  CICE_CATCH
+}
+
+// The stage on the batch (ice_step_mod.F90:286-422): see include/cice4_amd.h
+int cice_step_therm2_itd(cice_ctx* ctx, double dt, double yday, const cice_therm2_fields* f, int32_t* l_stop,
+                         int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  auto& t = c_->tb;
+  CICE_REQUIRE(f && l_stop && istop && jstop && bstop && stage, "NULL argument");
+  if (f->ncat == 1) throw Error{CICE_EUNSUPPORTED, "cice_step_therm2_itd: ncat = 1 (reduce_area) is not built"};
+  CICE_REQUIRE(f->ncat == NCAT, "cice_step_therm2_itd: ncat is not the library's");
+  CICE_REQUIRE(t.nb > 0, "cice_thermo_batch_alloc has not been called");
+  CICE_REQUIRE(c_->have_itd, "cice_itd_init has not been called");
+  CICE_REQUIRE(dt > 0.0, "dt");
+  CICE_REQUIRE(f->aicen && f->trcrn && f->vicen && f->vsnon && f->eicen && f->esnon && f->vicen_init && f->frain &&
+                   f->frzmlt && f->Tf && f->rside && f->tmask && f->aice && f->aice0 && f->fresh && f->fsalt && f->fhocn &&
+                   f->frazil && f->meltl && f->frz_onset, "cice_step_therm2_itd: NULL field");
+  const bool resident = f->state_resident != 0;
+  CICE_REQUIRE(resident || f->aicen_init, "cice_step_therm2_itd: aicen_init is needed without a resident state");
+  CICE_REQUIRE(!resident || (c_->have_thermo && c_->tp.nt_Tsfc - 1 == c_->ip.it_Tsfc),
+               "cice_step_therm2_itd: state_resident needs cice_thermo_init with the same nt_Tsfc");
+  CICE_REQUIRE(f->aicen_init || t.kept_aicen_init,
+               "cice_step_therm2_itd: aicen_init = NULL needs a cice_step_therm1 call on this batch in front");
+  hipStream_t s = c_->stream;
+  const size_t np = (size_t)t.nx * t.ny, n2 = np * t.nb, nc = n2 * NCAT;
+  if (c_->itd_b.n < 2 * nc + 12 * n2) c_->itd_b.alloc(2 * nc + 12 * n2);
+  if (c_->itd_bi.n < n2 + (size_t)t.nb) c_->itd_bi.alloc(n2 + (size_t)t.nb);
+  c_->itd_rec.alloc(ITD_REC_WORDS);
+  const bool timed = c_->itd_timed;
+  for (hipEvent_t& e : c_->itd_ev)
+    if (timed && !e) CICE_HIP(hipEventCreate(&e));
+  double* ainit = c_->itd_b.p;
+  double* vinit = c_->itd_b.p + nc;
+  double* d2 = c_->itd_b.p + 2 * nc;
+  int32_t* flag = c_->itd_bi.p + n2;
+  const int ntr = c_->ip.ntrcr, it_T = c_->ip.it_Tsfc;
+  auto upload = [&](bool state) {
+    c_->fan.fork(s);
+    if (state) {
+      t.aicen.upload(f->aicen, c_->cs()); t.vicen.upload(f->vicen, c_->cs()); t.vsnon.upload(f->vsnon, c_->cs());
+      t.eicen.upload(f->eicen, c_->cs()); t.esnon.upload(f->esnon, c_->cs());
+    }
+    for (int it = 0; it < ntr; ++it)
+      if (state || it != it_T) batch_tracer_copy(c_, it, f->trcrn, t.trcrn.p, hipMemcpyHostToDevice);
+    if (f->aicen_init) CICE_HIP(hipMemcpyAsync(ainit, f->aicen_init, nc * 8, hipMemcpyHostToDevice, c_->cs()));
+    CICE_HIP(hipMemcpyAsync(vinit, f->vicen_init, nc * 8, hipMemcpyHostToDevice, c_->cs()));
+    const double* in2[12] = {f->aice, f->aice0, f->frain, f->frzmlt, f->Tf, f->rside, f->fresh, f->fsalt, f->fhocn,
+                             nullptr, f->meltl, f->frz_onset};
+    for (int k = 0; k < 12; ++k)
+      if (in2[k]) CICE_HIP(hipMemcpyAsync(d2 + (size_t)k * n2, in2[k], n2 * 8, hipMemcpyHostToDevice, c_->cs()));
+    CICE_HIP(hipMemcpyAsync(c_->itd_bi.p, f->tmask, n2 * 4, hipMemcpyHostToDevice, c_->cs()));
+    c_->fan.join();
+    CICE_HIP(hipMemsetAsync(d2 + (size_t)I2_FRAZIL * n2, 0, n2 * 8, s));
+    CICE_HIP(hipMemsetAsync(c_->itd_rec.p, 0, ITD_REC_WORDS * 8, s));
+    CICE_HIP(hipMemsetAsync(flag, 0, (size_t)t.nb * 4, s));
+  };
+  ItdArgs a{};
+  a.p = c_->ip;
+  a.nx = t.nx; a.ny = t.ny; a.nblocks = t.nb; a.blk = t.blk.p; a.kitd = f->kitd != 0; a.dt = dt; a.yday = yday;
+  a.blockflag = flag; a.blockflag_out = flag; a.tmask = c_->itd_bi.p;
+  a.aicen = t.aicen.p; a.trcrn = t.trcrn.p; a.vicen = t.vicen.p; a.vsnon = t.vsnon.p; a.eicen = t.eicen.p;
+  a.esnon = t.esnon.p; a.vicen_init = vinit;
+  a.aicen_init = f->aicen_init ? ainit : t.mrg_in.p;   // NULL: the concentrations cice_step_therm1 kept for merge_fluxes
+  a.aice = d2 + I2_AICE * n2; a.aice0 = d2 + I2_AICE0 * n2; a.frain = d2 + I2_FRAIN * n2; a.frzmlt = d2 + I2_FRZMLT * n2;
+  a.Tf = d2 + I2_TF * n2; a.rside = d2 + I2_RSIDE * n2; a.fresh = d2 + I2_FRESH * n2; a.fsalt = d2 + I2_FSALT * n2;
+  a.fhocn = d2 + I2_FHOCN * n2; a.frazil = d2 + I2_FRAZIL * n2; a.meltl = d2 + I2_MELTL * n2;
+  a.frz_onset = d2 + I2_FRZ_ONSET * n2;
+  a.rec = c_->itd_rec.p;
+  auto run = [&](int bfail, int nlimit, int bend_add, int bend_melt) {
+    ItdArgs k = a;
+    k.bfail = bfail; k.nlimit = nlimit;
+    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[0], s));
+    itd_launch_rain_aggregate(k, s);
+    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[1], s));
+    if (k.kitd) itd_launch_linear(k, s);
+    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[2], s));
+    k.bend = bend_add;
+    itd_launch_add_new_ice(k, s);
+    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[3], s));
+    k.bend = bend_melt;
+    itd_launch_lateral_melt(k, s);
+    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[4], s));
+  };
+  unsigned long long r[ITD_REC_WORDS];
+  upload(!resident);
+  run(t.nb, 0, t.nb, t.nb);
+  itd_read_rec(c_, r);
+  for (int k = 0; k < 4 && timed; ++k) CICE_HIP(hipEventElapsedTime(&c_->itd_ms[k], c_->itd_ev[k], c_->itd_ev[k + 1]));
+  clear_stop(l_stop, istop, jstop);
+  *bstop = 0; *stage = 0;
+  int bl = -1, N = 0, ba = -1;
+  if (r[ITD_REC_SHIFT]) {
+    const unsigned long long v = r[ITD_REC_SHIFT] - 1;
+    bl = t.nb - 1 - (int)(v >> 8);
+    N = NCAT - (int)(v & 0xff);
+  }
+  if (r[ITD_REC_ADD]) ba = t.nb - 1 - (int)(r[ITD_REC_ADD] >> 32);
+  if (bl >= 0 || ba >= 0) {            // a stop: again from the caller's arrays, up to where the reference stops (itd.h)
+    const bool in_shift = bl >= 0 && (ba < 0 || bl <= ba);
+    const int bf = in_shift ? bl : ba;
+    upload(true);
+    run(bf, in_shift ? N : 0, in_shift ? bf : bf + 1, bf);
+    itd_read_rec(c_, r);
+    unsigned long long key = in_shift ? itd_shift_key(r, N) : (r[ITD_REC_ADD] & 0xffffffffull);
+    *l_stop = 1; *bstop = bf + 1; *stage = in_shift ? 1 : 2;
+    if (key) { *istop = (int32_t)((key - 1) % t.nx) + 1; *jstop = (int32_t)((key - 1) / t.nx) + 1; }
+  }
+  c_->fan.fork(s);
+  t.aicen.download(f->aicen, c_->cs()); t.vicen.download(f->vicen, c_->cs()); t.vsnon.download(f->vsnon, c_->cs());
+  t.eicen.download(f->eicen, c_->cs()); t.esnon.download(f->esnon, c_->cs());
+  for (int it = 0; it < ntr; ++it) batch_tracer_copy(c_, it, t.trcrn.p, f->trcrn, hipMemcpyDeviceToHost);
+  double* out2[12] = {f->aice, f->aice0, nullptr, nullptr, nullptr, nullptr, f->fresh, f->fsalt, f->fhocn, f->frazil,
+                      f->meltl, f->frz_onset};
+  for (int k = 0; k < 12; ++k)
+    if (out2[k]) CICE_HIP(hipMemcpyAsync(out2[k], d2 + (size_t)k * n2, n2 * 8, hipMemcpyDeviceToHost, c_->cs()));
+  c_->fan.join();
+  CICE_HIP(hipStreamSynchronize(s));
+  CICE_CATCH
+}
+
+int cice_therm2_itd_times(cice_ctx* ctx, int enable, float ms[4]) {
+  CICE_TRY(ctx)
+  c_->itd_timed = enable != 0;
+  for (int k = 0; k < 4 && ms; ++k) ms[k] = c_->itd_ms[k];
+  CICE_CATCH
+}
+
+}  // extern "C"

@@ -159,6 +159,46 @@ def test_sparse_list_travels_compact(ctx, orc, calc_Tsfc):
     assert lg == lc and lg[0] == 1 and (lg[1], lg[2]) == (ii[icells // 2], jj[icells // 2])
 
 
+@pytest.mark.parametrize("calc_Tsfc", [True, False])
+def test_compact_and_full_path_agree_at_the_switch(ctx, orc, calc_Tsfc):
+    """cice_thermo_vertical takes the compact path while 2 * icells <= nx * ny and the full one above.  On a block of
+    120 cells the first 60 entries of one list go the compact way and the first 61 the full way: the 60 common cells
+    come out bit for bit the same, each call equals the checker on its own list, and cells outside a list keep what
+    they held, with zero in the outputs (calc_Tsfc = F: fsurfn, fcondtopn, flatn are inputs and stay)."""
+    ny, nx = 10, 12
+    ctx.thermo_init(calc_Tsfc=calc_Tsfc); orc.init_thermo(calc_Tsfc=calc_Tsfc)
+    a, icells, ii, jj = synth.thermo_columns(ny, nx, 0, regime="mixed", seed=56, ice_frac=0.9)
+    assert icells >= 61
+    if not calc_Tsfc:
+        orc.init_thermo(); t = {k: v.copy() for k, v in a.items()}
+        assert orc.thermo_vertical(DT, icells, ii, jj, t, yday=120.0)[0] == 0
+        a = synth.known_tsfc_inputs(a, t, seed=4)
+        orc.init_thermo(calc_Tsfc=False)
+    flux_in = () if calc_Tsfc else ("fsurfn", "fcondtopn", "flatn")
+    got = {}
+    for m in (60, 61):
+        assert (2 * m <= nx * ny) == (m == 60)
+        ag = {k: v.copy() for k, v in a.items()}; ac = {k: v.copy() for k, v in a.items()}
+        lg = ctx.thermo_vertical(DT, m, ii, jj, ag, yday=120.0)
+        lc = orc.thermo_vertical(DT, m, ii, jj, ac, yday=120.0)
+        assert lg == lc == (0, 0, 0), (m, lg, lc)
+        _cmp(ag, ac, ("switch", m))
+        outside = np.ones((ny, nx), bool)
+        outside[jj[:m] - 1, ii[:m] - 1] = False
+        for k in CHECK:
+            if k in lib.THERMO_OUT and k not in flux_in:
+                assert np.all(ag[k][outside] == 0.0), (m, k)
+            else:
+                assert np.array_equal(ag[k][..., outside], a[k][..., outside]), (m, k)
+        got[m] = ag
+    common = np.zeros((ny, nx), bool)
+    common[jj[:60] - 1, ii[:60] - 1] = True
+    for k in CHECK:
+        assert np.array_equal(got[60][k][..., common], got[61][k][..., common]), k
+    assert not np.array_equal(got[60]["eicen"][..., common], a["eicen"][..., common])
+    ctx.thermo_init(); orc.init_thermo()
+
+
 def test_empty_list_and_all_melt(ctx, orc):
     ctx.thermo_init(); orc.init_thermo()
     a, icells, ii, jj = synth.thermo_columns(12, 20, 0, regime="summer", seed=3)
