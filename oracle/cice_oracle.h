@@ -157,6 +157,23 @@ int orc_thermo_vertical(const orc_thermo_cfg *c, int nx, int ny, double dt, int 
                         double *mlt_onset, double *frz_onset, double yday, int *istop,
                         int *jstop);
 
+/* Per-column trace of orc_thermo_vertical, for tests that count which branches their inputs reach.  trace: an
+ * (ny, nx) int32 plane, or NULL (the default) for none.  While one is set, every column of the list writes its word:
+ * the solver's iteration count in the low byte and the ORC_TR_* bits above it; cells outside the list are not
+ * touched.  The trace is written only: no result depends on it. */
+#define ORC_TR_TSF_RESET 0x100u       /* Tsf came out above 0 and was reset (:1843) */
+#define ORC_TR_TSF_HALVED 0x200u      /* oscillating Tsf: the step was halved (:1853) */
+#define ORC_TR_COND2B_HALVED 0x400u   /* calc_Tsfc = F: oscillating top-layer temperature (:1961) */
+#define ORC_TR_LAYER_AT_TMLT 0x800u   /* an ice layer reached its melting temperature: reduce_kh (:1948) */
+#define ORC_TR_KH_REDUCED 0x1000u     /* ... and kh was scaled inside the iteration (:2062) */
+#define ORC_TR_COLD 0x2000u           /* an iteration used the matrix rows of a cold surface */
+#define ORC_TR_MELTING 0x4000u        /* an iteration used the matrix rows of a melting surface */
+#define ORC_TR_BOTTOM_INTO_SNOW 0x8000u  /* bottom melt went through all the ice and took snow (:3984) */
+#define ORC_TR_SNOICE_NO_ICE 0x10000u /* freeboard turned snow into ice where no ice was left (:4315) */
+#define ORC_TR_STOPPED 0x20000000u    /* the reference would stop at this column */
+#define ORC_TR_LISTED 0x40000000u     /* the column was in the list */
+void orc_set_thermo_trace(int32_t *trace);
+
 void orc_frzmlt_bottom_lateral(const orc_thermo_cfg *c, int nx, int ny, int ilo, int ihi, int jlo,
                                int jhi, double dt, const double *aice, const double *frzmlt,
                                const double *eicen, const double *esnon, const double *sst,

@@ -236,13 +236,26 @@ class Oracle:
                    "fswabsn", "flwoutn", "evapn", "freshn", "fsaltn", "fhocnn", "meltt", "melts",
                    "meltb", "congel", "snoice", "mlt_onset", "frz_onset")
 
-    def thermo_vertical(self, dt, icells, indxi, indxj, a, yday=1.0):
+    # bits of the per-column trace (cice_oracle.h: ORC_TR_*); the low byte holds the solver's iteration count
+    TRACE_BITS = dict(tsf_reset=0x100, tsf_halved=0x200, cond2b_halved=0x400, layer_at_Tmlt=0x800, kh_reduced=0x1000,
+                      cold=0x2000, melting=0x4000, bottom_into_snow=0x8000, snoice_after_ice_gone=0x10000,
+                      stopped=0x20000000, listed=0x40000000)
+
+    def thermo_vertical(self, dt, icells, indxi, indxj, a, yday=1.0, trace=None):
+        """trace: None, or an int32 (ny, nx) array that every listed column writes its trace word into (tests that
+        count branches); the results do not depend on it."""
         ny, nx = a["aicen"].shape
         istop = C.c_int(0); jstop = C.c_int(0)
-        ls = self.lib.orc_thermo_vertical(C.byref(self.tc), C.c_int(nx), C.c_int(ny), C.c_double(dt),
-                                          C.c_int(icells), _p(indxi), _p(indxj),
-                                          *[_p(a[k]) for k in self.THERMO_ARGS], C.c_double(yday),
-                                          C.byref(istop), C.byref(jstop))
+        if trace is not None:
+            assert trace.dtype == np.int32 and trace.shape == (ny, nx)
+        self.lib.orc_set_thermo_trace(_p(trace))
+        try:
+            ls = self.lib.orc_thermo_vertical(C.byref(self.tc), C.c_int(nx), C.c_int(ny), C.c_double(dt),
+                                              C.c_int(icells), _p(indxi), _p(indxj),
+                                              *[_p(a[k]) for k in self.THERMO_ARGS], C.c_double(yday),
+                                              C.byref(istop), C.byref(jstop))
+        finally:
+            self.lib.orc_set_thermo_trace(None)
         return ls, istop.value, jstop.value
 
     def frzmlt_bottom_lateral(self, ilo, ihi, jlo, jhi, dt, aice, frzmlt, eicen, esnon, sst, Tf,

@@ -44,6 +44,11 @@ static inline double dmax(double a, double b) { return a > b ? a : b; }
 /* diagnostics for tests/bench: histogram of temperature-solver iterations per column */
 long orc_iter_hist[101];
 
+/* per-column trace (tests only, see cice_oracle.h): where to write it, NULL = nowhere.  Only ever written, never read
+ * back into the arithmetic. */
+static int32_t *g_trace = NULL;
+void orc_set_thermo_trace(int32_t *trace) { g_trace = trace; }
+
 /* ice_therm_vertical.F90:533-584 */
 void orc_init_thermo(int heat_capacity, int calc_Tsfc, int conduct, double ustar_min,
                      orc_thermo_cfg *c) {
@@ -81,6 +86,7 @@ enum {
 
 typedef struct {
   double hin, hsn, hilyr, hslyr, Tsf, einit, efinal, fcondbot, hsn_new;
+  uint32_t trace; /* ORC_TR_* bits of the branches this column took */
   double qin[NI], Tin[NI], qsn[NS], Tsn[NS];
 } column;
 
@@ -275,6 +281,7 @@ static int temperature_changes(const orc_thermo_cfg *c, double dt, column *col, 
       if (f->fsurfn < f->fcondtopn) col->Tsf = dmin(col->Tsf, -puny);
       Tsf_start = col->Tsf;
       l_cold = (col->Tsf <= -puny);
+      col->trace |= l_cold ? ORC_TR_COLD : ORC_TR_MELTING;
     }
 
     /* get_matrix_elements_calc_Tsfc :2540-2751 / _know_Tsfc :2871-3048 (rows 0-based here) */
@@ -368,6 +375,7 @@ static int temperature_changes(const orc_thermo_cfg *c, double dt, column *col, 
         dTsf = -Tsf_start;
         if (c->l_brine) avg_Tsi = c1;
         converged = 0;
+        col->trace |= ORC_TR_TSF_RESET;
       } else if (niter > 1 && Tsf_start <= -puny && fabs(dTsf) > puny && fabs(dTsf_prev) > puny &&
                  -dTsf / (dTsf_prev + puny * puny) > p5) {
         if (c->l_brine) {
@@ -376,6 +384,7 @@ static int temperature_changes(const orc_thermo_cfg *c, double dt, column *col, 
         }
         dTsf = p5 * dTsf;
         converged = 0;
+        col->trace |= ORC_TR_TSF_HALVED;
       }
       col->Tsf = col->Tsf + avg_Tsf * p5 * (Tsf_start - col->Tsf);
     }
@@ -395,6 +404,7 @@ static int temperature_changes(const orc_thermo_cfg *c, double dt, column *col, 
         dqmat[k] = rhoi * dTmat[k] * (cp_ice - Lfresh * Tmlt[k] / (Tin[k] * Tin[k]));
         Tin[k] = Tmlt[k];
         reduce_kh[k] = 1;
+        col->trace |= ORC_TR_LAYER_AT_TMLT;
       }
       if (k == 0 && !calc) { /* condition 2b :1961-1975 */
         double dTi1 = Tin[k] - Tin_start[k];
@@ -403,6 +413,7 @@ static int temperature_changes(const orc_thermo_cfg *c, double dt, column *col, 
           if (c->l_brine) avg_Tsi = c1;
           dTi1 = p5 * dTi1;
           converged = 0;
+          col->trace |= ORC_TR_COND2B_HALVED;
         }
         dTi1_prev = dTi1;
       }
@@ -432,10 +443,12 @@ static int temperature_changes(const orc_thermo_cfg *c, double dt, column *col, 
           double frac = dmax(0.5 * (c1 - ferr / fabs(f->fcondtopn - col->fcondbot)), p1);
           kh[k + NS] = kh[k + NS] * frac;
           kh[k + NS - 1] = kh[k + NS] * frac;
+          col->trace |= ORC_TR_KH_REDUCED;
         }
     }
   }
   orc_iter_hist[niter_done]++;
+  col->trace |= (uint32_t)niter_done; /* <= nitermax = 100: the low byte */
   if (calc) { /* :2136-2145 */
     f->flwoutn = f->flwoutn + dTsf_prev * dflwout_dT;
     f->fsensn = f->fsensn + dTsf_prev * dfsens_dT;
@@ -546,6 +559,7 @@ static void thickness_changes(const orc_thermo_cfg *c, double dt, double yday, c
   }
   for (int k = NS - 1; k >= 0; k--) { /* :3984-4000 */
     dhs = dmax(-dzs[k], ebot_mlt / qsn[k]);
+    if (dhs < c0) col->trace |= ORC_TR_BOTTOM_INTO_SNOW;
     dzs[k] = dzs[k] + dhs;
     ebot_mlt = ebot_mlt - dhs * qsn[k];
     ebot_mlt = dmax(ebot_mlt, c0);
@@ -571,6 +585,7 @@ static void thickness_changes(const orc_thermo_cfg *c, double dt, double yday, c
     if (wk1 > puny && col->hsn > puny) {
       dhsn = dmin(wk1 * rhoi / rhow, col->hsn);
       dhin = dhsn * rhos / rhoi;
+      if (dhin > puny && !(col->hin > c0)) col->trace |= ORC_TR_SNOICE_NO_ICE;
     }
     for (int k = NS - 1; k >= 0; k--)
       if (dhin > puny) {
@@ -686,8 +701,10 @@ int orc_thermo_vertical(const orc_thermo_cfg *c, int nx, int ny, double dt, int 
     double ei[NI], es[NS];
     for (int k = 0; k < NI; k++) ei[k] = eicen[k * np + q];
     for (int k = 0; k < NS; k++) es[k] = esnon[k * np + q];
+    col.trace = ORC_TR_LISTED;
     int stage = init_vertical_profile(c, aicen[q], vicen[q], vsnon[q], Tsfcn[q], ei, es, &col);
     if (stage != ST_OK) {
+      if (g_trace) g_trace[q] = (int32_t)(col.trace | ORC_TR_STOPPED);
       long key = (long)stage * icells + ij;
       if (best_key < 0 || key < best_key) best_key = key;
       continue;
@@ -701,6 +718,7 @@ int orc_thermo_vertical(const orc_thermo_cfg *c, int nx, int ny, double dt, int 
     f.fsurfn = fsurfn[q]; f.fcondtopn = fcondtopn[q]; f.flatn = flatn[q];
     f.fsensn = f.fswabsn = f.flwoutn = c0;
     int conv = temperature_changes(c, dt, &col, &f);
+    if (g_trace) g_trace[q] = (int32_t)(col.trace | (conv ? 0 : ORC_TR_STOPPED));
     /* inout fields are written back even for a failing column (the reference has
      * modified them by the time it stops) */
     fswsfc[q] = f.fswsfc; fswint[q] = f.fswint;
@@ -717,6 +735,7 @@ int orc_thermo_vertical(const orc_thermo_cfg *c, int nx, int ny, double dt, int 
     g.meltt = g.melts = g.meltb = g.congel = g.snoice = c0;
     g.mlt_onset = mlt_onset[q]; g.frz_onset = frz_onset[q];
     thickness_changes(c, dt, yday, &col, &f, &g);
+    if (g_trace) g_trace[q] = (int32_t)col.trace;
     fhocnn[q] = g.fhocnn; evapn[q] = g.evapn; meltt[q] = g.meltt; melts[q] = g.melts;
     meltb[q] = g.meltb; congel[q] = g.congel; snoice[q] = g.snoice;
     mlt_onset[q] = g.mlt_onset; frz_onset[q] = g.frz_onset;
@@ -724,6 +743,7 @@ int orc_thermo_vertical(const orc_thermo_cfg *c, int nx, int ny, double dt, int 
       double einp = (f.fsurfn - f.flatn + f.fswint - g.fhocnn - g.fsnow * Lfresh) * dt;
       double ferr = fabs(col.efinal - col.einit - einp) / dt;
       if (ferr > ferrmax) {
+        if (g_trace) g_trace[q] = (int32_t)(col.trace | ORC_TR_STOPPED);
         long key = (long)ST_ECONS * icells + ij;
         if (best_key < 0 || key < best_key) best_key = key;
         continue;

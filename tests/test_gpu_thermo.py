@@ -7,6 +7,7 @@ elsewhere); only frzmlt_bottom_lateral (`**1.36` -> pow) keeps the 1e-10 bound. 
 import numpy as np
 import pytest
 
+import thermo_case as tc
 from cice4_amd import lib, synth
 from conftest import relerr, TOL_EXP, TOL_POW
 
@@ -36,6 +37,73 @@ def _cmp(a_gpu, a_cpu, tag=""):
     for k in CHECK:
         e = frel(k, a_gpu[k], a_cpu[k])
         assert e <= TOL, (tag, k, e)
+
+
+def _melted_come_back_exactly(a, ag, ac, icells, ii, jj):
+    """the columns of the list that the checker melts away: the device returns aicen = vicen = vsnon = eicen = esnon = 0
+    and Tsfc = Tbot there, exactly.  Returns their number."""
+    listed = np.zeros(a["aicen"].shape, bool)
+    listed[jj[:icells] - 1, ii[:icells] - 1] = True
+    gone = listed & (ac["aicen"] == 0.0)
+    for k in ("aicen", "vicen", "vsnon"):
+        assert np.array_equal(ag[k][gone], np.zeros(gone.sum())), k
+    for k in ("eicen", "esnon"):
+        assert np.array_equal(ag[k][:, gone], np.zeros((ag[k].shape[0], gone.sum()))), k
+    assert np.array_equal(ag["trcrn"][0][gone], a["Tbot"][gone])
+    assert np.array_equal(ag["aicen"] == 0.0, ac["aicen"] == 0.0)       # and no other column
+    return int(gone.sum())
+
+
+def _outside_untouched(a, ag, icells, ii, jj, flux_in=()):
+    """cells outside the list keep what they held; the outputs are zero there"""
+    outside = np.ones(a["aicen"].shape, bool)
+    outside[jj[:icells] - 1, ii[:icells] - 1] = False
+    for k in CHECK:
+        if k in lib.THERMO_OUT and k not in flux_in:
+            assert np.all(ag[k][outside] == 0.0), k
+        else:
+            assert np.array_equal(ag[k][..., outside], a[k][..., outside]), k
+
+
+@pytest.mark.parametrize("name", list(tc.LIST_SETS))
+@pytest.mark.parametrize("conduct", ["MU71", "bubbly"])
+def test_extreme_columns_match_oracle(ctx, orc, name, conduct):
+    """The list kernel on the sets of tests/thermo_case.py: columns that melt through whole layers from above and from
+    below, columns that melt away, interior layers at their melting temperature with kh scaled inside the solver's
+    iteration (tests/test_thermo_branches.py holds every set to its branches; tests/test_oracle_vs_ref.py pins the
+    checker to the reference on the same sets).  Four recipes x five categories at 12 x 20, and at 37 x 70 one set the
+    compact way and one the full way, with column counts that are no multiple of 64 or 256."""
+    ctx.thermo_init(conduct=conduct); orc.init_thermo(conduct=conduct)
+    gone = 0
+    for n, a, icells, ii, jj in tc.list_set(name):
+        ag = {k: v.copy() for k, v in a.items()}; ac = {k: v.copy() for k, v in a.items()}
+        lg = ctx.thermo_vertical(DT, icells, ii, jj, ag, yday=tc.YDAY)
+        lc = orc.thermo_vertical(DT, icells, ii, jj, ac, yday=tc.YDAY)
+        assert lg == lc == (0, 0, 0), (name, n, lg, lc)
+        _cmp(ag, ac, (name, conduct, n))
+        gone += _melted_come_back_exactly(a, ag, ac, icells, ii, jj)
+        _outside_untouched(a, ag, icells, ii, jj)
+    assert gone >= 8
+    ctx.thermo_init(); orc.init_thermo()
+
+
+@pytest.mark.parametrize("name", tc.RECIPE_SETS)
+@pytest.mark.parametrize("conduct", ["MU71", "bubbly"])
+def test_extreme_columns_known_Tsfc_bit_exact(ctx, orc, name, conduct):
+    """calc_Tsfc = F on the recipe sets (the columns the perturbed fluxes stop have left the lists: tc.known_tsfc_set):
+    no exp() on this path, so device == checker bit for bit."""
+    sets = tc.known_tsfc_set(orc, name, conduct)
+    ctx.thermo_init(calc_Tsfc=False, conduct=conduct)
+    for n, b, icells, ii, jj, _ in sets:
+        bg = {k: v.copy() for k, v in b.items()}; bc = {k: v.copy() for k, v in b.items()}
+        lg = ctx.thermo_vertical(DT, icells, ii, jj, bg, yday=tc.YDAY)
+        lc = orc.thermo_vertical(DT, icells, ii, jj, bc, yday=tc.YDAY)
+        assert lg == lc == (0, 0, 0), (name, n, lg, lc)
+        for k in CHECK:
+            assert np.array_equal(bg[k], bc[k]), (name, conduct, n, k)
+        _melted_come_back_exactly(b, bg, bc, icells, ii, jj)
+        _outside_untouched(b, bg, icells, ii, jj, flux_in=("fsurfn", "fcondtopn", "flatn"))
+    ctx.thermo_init(); orc.init_thermo()
 
 
 @pytest.mark.parametrize("regime", ["winter", "summer", "mixed"])
@@ -205,15 +273,15 @@ def test_empty_list_and_all_melt(ctx, orc):
     ag = {k: v.copy() for k, v in a.items()}
     assert ctx.thermo_vertical(DT, 0, ii, jj, ag) == (0, 0, 0)
     assert np.array_equal(ag["vicen"], a["vicen"]) and np.all(ag["flatn"] == 0.0)
-    # very thin ice under strong heating melts away completely: state is zeroed, Tsfc = Tbot
-    a["vicen"] *= 0.02; a["eicen"] *= 0.02; a["vsnon"] *= 0.0; a["esnon"] *= 0.0
+    # very thin ice under strong heating melts away completely: state is zeroed, Tsfc = Tbot.  The snow stays (without
+    # it Sswabs and fswint would be shortwave absorbed by nothing, and the reference stops in its energy check).
+    a["vicen"] *= 0.02; a["eicen"] *= 0.02
     a["fbot"][:] = -400.0
     ag = {k: v.copy() for k, v in a.items()}; ac = {k: v.copy() for k, v in a.items()}
     lg = ctx.thermo_vertical(DT, icells, ii, jj, ag); lc = orc.thermo_vertical(DT, icells, ii, jj, ac)
-    assert lg == lc
-    if lc[0] == 0:
-        _cmp(ag, ac, "melt")
-        assert (ac["aicen"][jj[:icells] - 1, ii[:icells] - 1] == 0).any()
+    assert lg == lc == (0, 0, 0)
+    _cmp(ag, ac, "melt")
+    assert _melted_come_back_exactly(a, ag, ac, icells, ii, jj) >= 8
 
 
 def test_error_reporting_matches_reference_order(ctx, orc):
@@ -236,37 +304,9 @@ def test_error_reporting_matches_reference_order(ctx, orc):
     assert (lc[1], lc[2]) == (ii[bad[1]], jj[bad[1]])
 
 
-def _batch_inputs(ny, nx, nb, seed):
-    """Module-array-shaped inputs of the batched step from per-category column sets."""
-    NC, NI, NS = 5, 4, 1
-    out = {k: None for k in lib.THERMO_STATE + lib.THERMO_FORCING + lib.THERMO_CAT_IN + lib.THERMO_SW
-           + lib.THERMO_OUT + lib.THERMO_ONSET}
-    z = lambda *shape: np.zeros(shape)
-    out.update(aicen=z(nb, NC, ny, nx), trcrn=z(nb, NC, 5, ny, nx), vicen=z(nb, NC, ny, nx),
-               vsnon=z(nb, NC, ny, nx), eicen=z(nb, NC * NI, ny, nx), esnon=z(nb, NC * NS, ny, nx),
-               lhcoef=z(nb, NC, ny, nx), shcoef=z(nb, NC, ny, nx), fswsfc=z(nb, NC, ny, nx),
-               fswint=z(nb, NC, ny, nx), fswthrun=z(nb, NC, ny, nx), Sswabs=z(nb, NC, NS, ny, nx),
-               Iswabs=z(nb, NC, NI, ny, nx), mlt_onset=z(nb, ny, nx), frz_onset=z(nb, ny, nx))
-    for k in lib.THERMO_FORCING:
-        out[k] = z(nb, ny, nx)
-    for k in lib.THERMO_OUT:
-        out[k] = np.full((nb, NC, ny, nx), 9.0)
-    percat = {}
-    for b in range(nb):
-        for n in range(NC):
-            a, icells, ii, jj = synth.thermo_columns(ny, nx, n, regime="mixed", seed=seed + 17 * b,
-                                                     ice_frac=0.8)
-            percat[(b, n)] = (a, icells, ii, jj)
-            for k in ("aicen", "vicen", "vsnon", "lhcoef", "shcoef", "fswsfc", "fswint", "fswthrun"):
-                out[k][b, n] = a[k]
-            out["trcrn"][b, n] = a["trcrn"]
-            out["eicen"][b, n * NI:(n + 1) * NI] = a["eicen"]
-            out["esnon"][b, n * NS:(n + 1) * NS] = a["esnon"]
-            out["Sswabs"][b, n] = a["Sswabs"]; out["Iswabs"][b, n] = a["Iswabs"]
-            if n == 0:
-                for k in lib.THERMO_FORCING + ("mlt_onset", "frz_onset"):
-                    out[k][b] = a[k]
-    return out, percat
+def _batch_inputs(ny, nx, nb, seed, recipe=None):
+    """Module-array-shaped inputs of the batched step from per-category column sets (recipe: see tc.batch_inputs)."""
+    return tc.batch_inputs(ny, nx, nb, seed, recipe=recipe)
 
 
 def test_batched_step_equals_per_category_calls(ctx, orc):
@@ -306,16 +346,65 @@ def test_batched_step_equals_per_category_calls(ctx, orc):
     assert st["n_updates"] == nupd
 
 
-@pytest.mark.parametrize("chunk,group", [(256, 1), (512, 8), (2048, 16), (256, 32)])
-def test_sorted_columns_give_the_same_bits(ctx, chunk, group):
+@pytest.mark.parametrize("sort_chunk", [0, 256])
+@pytest.mark.parametrize("conduct", ["MU71", "bubbly"])
+def test_extreme_batch_equals_per_category_calls(ctx, orc, conduct, sort_chunk):
+    """cice_thermo_batch_step on the extreme batch (tc.BATCH: one recipe per block), as k_thermo_dense and with the
+    columns dealt to the lanes in sorted order (k_thermo_perm), against the per-category calls of the checker: every
+    field, n_updates, the onset dates the categories of a cell share, the melted-away columns exactly, and the solver
+    iterations the device keeps per column against the checker's trace."""
+    ctx.thermo_init(conduct=conduct); orc.init_thermo(conduct=conduct)
+    s = tc.BATCH
+    ny, nx, nb = s["ny"], s["nx"], s["nb"]
+    batch, percat = _batch_inputs(ny, nx, nb, seed=s["seed"], recipe=s["recipe"])
+    ctx.thermo_batch_alloc(nx, ny, nb)
+    ctx.thermo_set_option("sort_chunk", sort_chunk); ctx.thermo_set_option("sort_group", 8)
+    ctx.thermo_batch_upload(batch)
+    st = ctx.thermo_batch_step(DT, yday=s["yday"])
+    ctx.thermo_set_option("sort_chunk", 0)
+    assert st["l_stop"] == 0
+    ctx.thermo_batch_download(batch)
+    niter = ctx.evp_debug("thermo_niter").view(np.uint8)[:nb * 5 * ny * nx].reshape(nb, 5, ny, nx)
+    res = tc.batch_checker_calls(orc, percat, nb, s["yday"])
+    nupd = gone = 0
+    for (b, n), (before, ac, trace, lc) in res.items():
+        assert lc == (0, 0, 0)
+        icells = percat[(b, n)][1]
+        nupd += icells
+        for k in ("aicen", "vicen", "vsnon", "fswsfc", "fswint") + lib.THERMO_OUT:
+            assert frel(k, batch[k][b, n], ac[k]) <= TOL, (b, n, k)
+        assert relerr(batch["trcrn"][b, n], ac["trcrn"]) <= TOL
+        assert relerr(batch["eicen"][b, n * 4:(n + 1) * 4], ac["eicen"]) <= TOL
+        assert relerr(batch["esnon"][b, n:n + 1], ac["esnon"]) <= TOL
+        assert relerr(batch["Iswabs"][b, n], ac["Iswabs"]) <= TOL
+        assert relerr(batch["Sswabs"][b, n], ac["Sswabs"]) <= TOL
+        ag = dict(aicen=batch["aicen"][b, n], vicen=batch["vicen"][b, n], vsnon=batch["vsnon"][b, n],
+                  eicen=batch["eicen"][b, n * 4:(n + 1) * 4], esnon=batch["esnon"][b, n:n + 1], trcrn=batch["trcrn"][b, n])
+        gone += _melted_come_back_exactly(before, ag, ac, *percat[(b, n)][1:])
+        listed = (trace & tc.TRACE["listed"]) != 0
+        assert np.array_equal(niter[b, n][listed], (trace & 0xff)[listed].astype(np.uint8)), (b, n)
+        if n == 4:
+            assert np.array_equal(batch["mlt_onset"][b], ac["mlt_onset"])
+            assert np.array_equal(batch["frz_onset"][b], ac["frz_onset"])
+            assert not np.array_equal(ac["mlt_onset"], percat[(b, 0)][0]["mlt_onset"])
+    assert st["n_updates"] == nupd and gone >= 8
+    ctx.thermo_init(); orc.init_thermo()
+
+
+@pytest.mark.parametrize("chunk,group,recipe", [(256, 1, None), (512, 8, None), (2048, 16, None), (256, 32, None),
+                                                (512, 8, tc.BATCH["recipe"])],
+                         ids=["256-1", "512-8", "2048-16", "256-32", "512-8-extreme"])
+def test_sorted_columns_give_the_same_bits(ctx, chunk, group, recipe):
     """cice_thermo_set_option("sort_chunk", C): the columns of every chunk are dealt to the lanes in the order of the
     work they are expected to take (previous step's solver iterations, snow, cold / melting).  Which lane a column sits
     in changes nothing in its arithmetic: every field equals the unsorted step bit for bit, in the first step (no
     iteration counts yet) and in a second one (sorted by the first step's counts); planes that are no multiple of the
-    chunk, two blocks, ice-free and ghost cells inside the chunks."""
+    chunk, two blocks, ice-free and ghost cells inside the chunks.  On the extreme batch (tc.BATCH at this size) the
+    columns take 1 to 40 and more iterations and the second step's sort has a real spread."""
     ctx.thermo_init()
     ny, nx, nb = 29, 43, 2
-    batch, _ = _batch_inputs(ny, nx, nb, seed=33)
+    assert (ny, nx, nb, 33) == tuple(tc.SORTED[k] for k in ("ny", "nx", "nb", "seed"))
+    batch, _ = _batch_inputs(ny, nx, nb, seed=33, recipe=recipe)
     keys = ("aicen", "vicen", "vsnon", "trcrn", "eicen", "esnon", "fswsfc", "fswint", "Sswabs", "Iswabs", "mlt_onset",
             "frz_onset") + lib.THERMO_OUT
     res = {}
@@ -334,6 +423,8 @@ def test_sorted_columns_give_the_same_bits(ctx, chunk, group):
     ctx.thermo_set_option("sort_chunk", 0)
     for step in range(2):
         assert res[0][step][1] == res[chunk][step][1] > 0
+        if recipe is not None:
+            assert ((batch["aicen"] > 0) & (res[chunk][step][0]["aicen"] == 0)).sum() >= 8
         for k in keys:
             assert np.array_equal(res[0][step][0][k], res[chunk][step][0][k]), (step, k)
 
@@ -376,17 +467,21 @@ def test_step_therm1_single_call_equals_the_separate_calls(ctx):
     """cice_step_therm1 (one upload, frzmlt_bottom_lateral -> thermo_vertical x ncat -> merge_fluxes on the device, one
     download) against the same work through the separate entries (frzmlt per block, batch upload / step / merge /
     download), which the tests above pin to the checker: every field bit for bit."""
+    _step_therm1_both_ways(ctx, 22, 34, 2, 150.0, *tc.therm1_inputs(22, 34, 2, seed=35))
+
+
+def test_step_therm1_single_call_on_the_extreme_batch(ctx):
+    """the same on tc.THERM1: a melt potential that makes fbot of the order of -1500 W m-2 under the recipes' thin ice
+    and strong shortwave, so that both ways melt columns through their layers and away"""
+    s = tc.THERM1
+    a, b_ = _step_therm1_both_ways(ctx, s["ny"], s["nx"], s["nb"], s["yday"],
+                                   *tc.therm1_inputs(s["ny"], s["nx"], s["nb"], s["seed"], s["recipe"], s["frzmlt"], s["dsst"]))
+    assert a["fbot"].min() < -1000.0
+    assert ((b_["aicen_in"] > 0) & (b_["aicen"] == 0)).sum() >= 8
+
+
+def _step_therm1_both_ways(ctx, ny, nx, nb, yday, batch, percat, fz, pc, acc0):
     ctx.thermo_init()
-    ny, nx, nb = 22, 34, 2
-    batch, percat = _batch_inputs(ny, nx, nb, seed=35)
-    rng = np.random.default_rng(6)
-    aice = np.ascontiguousarray(batch["aicen"].sum(axis=1))
-    fz = dict(aice=aice, frzmlt=np.ascontiguousarray(rng.uniform(-60, 20, (nb, ny, nx))),
-              Tf=np.full((nb, ny, nx), -1.8), strocnxT=np.ascontiguousarray(rng.uniform(-0.2, 0.2, (nb, ny, nx))),
-              strocnyT=np.ascontiguousarray(rng.uniform(-0.2, 0.2, (nb, ny, nx))))
-    fz["sst"] = fz["Tf"] + rng.uniform(0, 0.5, (nb, ny, nx))
-    pc = {k: np.ascontiguousarray(rng.uniform(-1, 1, batch["aicen"].shape)) for k in ("strairxn", "strairyn", "Trefn", "Qrefn")}
-    acc0 = {k: np.ascontiguousarray(rng.uniform(-1, 1, (nb, ny, nx))) for k in lib.MERGE_ORDER}
     # (a) separate entries
     a = {k: v.copy() for k, v in batch.items()}
     rs = np.zeros((nb, ny, nx))
@@ -397,7 +492,7 @@ def test_step_therm1_single_call_equals_the_separate_calls(ctx):
         a["Tbot"][b] = tb; a["fbot"][b] = fb; rs[b] = r
     ctx.thermo_batch_alloc(nx, ny, nb)
     ctx.thermo_batch_upload(a)
-    st_a = ctx.thermo_batch_step(DT, yday=150.0)
+    st_a = ctx.thermo_batch_step(DT, yday=yday)
     acc_a = {k: v.copy() for k, v in acc0.items()}
     ctx.thermo_batch_merge(dict(pc, aicen_init=batch["aicen"].copy()), acc_a)
     ctx.thermo_batch_download(a)
@@ -405,7 +500,7 @@ def test_step_therm1_single_call_equals_the_separate_calls(ctx):
     b_ = {k: v.copy() for k, v in batch.items()}
     fzb = dict(fz, Tbot=np.zeros((nb, ny, nx)), fbot=np.zeros((nb, ny, nx)), rside=np.zeros((nb, ny, nx)))
     acc_b = {k: v.copy() for k, v in acc0.items()}
-    st_b = ctx.step_therm1(DT, 150.0, b_, fzb, pc, acc_b)
+    st_b = ctx.step_therm1(DT, yday, b_, fzb, pc, acc_b)
     assert st_b["l_stop"] == st_a["l_stop"] == 0 and st_b["n_updates"] == st_a["n_updates"] > 0
     assert np.array_equal(fzb["Tbot"], a["Tbot"]) and np.array_equal(fzb["fbot"], a["fbot"]) and np.array_equal(fzb["rside"], rs)
     assert np.abs(fzb["fbot"]).max() > 0 and np.abs(rs).max() > 0
@@ -415,6 +510,8 @@ def test_step_therm1_single_call_equals_the_separate_calls(ctx):
         assert np.array_equal(b_[k], a[k]), k
     for k in lib.MERGE_ORDER:
         assert np.array_equal(acc_b[k], acc_a[k]), k
+    b_["aicen_in"] = batch["aicen"]
+    return a, b_
 
 
 def test_thermo_state_handed_to_the_dynamics_on_the_device(ctx):
@@ -423,20 +520,28 @@ def test_thermo_state_handed_to_the_dynamics_on_the_device(ctx):
     `aggregate`, ice_itd.F90:279) and the next evp(dt) uploads neither them nor aice, vice, vsno, aice0.  The result
     equals the two PCIe calls -- download the thermo state, aggregate on the host, evp(dt) with everything uploaded --
     bit for bit."""
+    _hand_off_both_ways(ctx, None)
+
+
+def test_thermo_state_of_an_extreme_step_handed_to_the_dynamics(ctx):
+    """the same behind tc.ADOPT, a step that empties categories: they reach the dynamics as zeros, and the aggregates the
+    device forms equal the sum in category order that the host forms in numpy (the dynamics' results are the same bits)"""
+    before, after = _hand_off_both_ways(ctx, tc.ADOPT["recipe"])
+    emptied = (before["aicen"] > 0) & (after["aicen"] == 0)
+    assert emptied.sum() >= 8 and np.all(after["vicen"][emptied] == 0) and np.all(after["vsnon"][emptied] == 0)
+
+
+def _hand_off_both_ways(ctx, recipe):
     DTE, NDTE_ = 3600.0, 24
-    nxg, nyg = 70, 44
+    nxg, nyg = tc.ADOPT["nxg"], tc.ADOPT["nyg"]
     dom = ctx.domain_create(nxg, nyg, nxg, nyg, ew=1, ns=0)
     ny, nx, nb = dom["ny"], dom["nx"], 1
+    assert (ny, nx) == (tc.ADOPT["ny"], tc.ADOPT["nx"])
     gg = synth.global_grid(nxg, nyg, perturb=0.1, land_frac=0.03, seed=5)
     grid = synth.block_fields(gg, dom)
     ctx.thermo_init()
-    batch, _ = _batch_inputs(ny, nx, nb, seed=9)
-    tot = batch["aicen"].sum(axis=1, keepdims=True)      # concentrations of a cell add up to at most 0.95
-    sc = np.where(tot > 0.95, 0.95 / np.maximum(tot, 1e-30), 1.0)
-    for k in ("aicen", "vicen", "vsnon"):
-        batch[k] = np.ascontiguousarray(batch[k] * sc)
-    batch["eicen"] = np.ascontiguousarray(batch["eicen"] * sc)
-    batch["esnon"] = np.ascontiguousarray(batch["esnon"] * sc)
+    batch, _ = tc.adopt_batch(ny, nx, recipe, seed=tc.ADOPT["seed"])   # concentrations of a cell add up to at most 0.95
+    before = {k: batch[k].copy() for k in ("aicen", "vicen", "vsnon")}
     ctx.thermo_batch_alloc(nx, ny, nb)
     ctx.thermo_batch_upload(batch)
     assert ctx.thermo_batch_step(DTE, yday=150.0)["l_stop"] == 0
@@ -465,6 +570,7 @@ def test_thermo_state_handed_to_the_dynamics_on_the_device(ctx):
     assert np.abs(a["uvel"]).max() > 1e-4 and a["strength"].max() > 0
     with pytest.raises(lib.CiceError):       # without a fresh hand-off the six fields are required again
         ctx.evp(DTE, b)
+    return before, batch
 
 
 def test_frzmlt_bottom_lateral(ctx, orc):

@@ -7,6 +7,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import thermo_case as tc
 from cice4_amd import lib, synth
 
 DT, NDTE = 3600.0, 120
@@ -171,6 +172,61 @@ def test_thermo_vertical_known_Tsfc_bit_exact(ref_gx3, orc, conduct):
             assert not np.array_equal(b1["eicen"], b["eicen"])
             assert not np.array_equal(b1["eicen"], t["eicen"])         # the perturbed fluxes matter
             assert not b1["fsensn"].any() and not b1["flwoutn"].any()  # never assigned (:299-306)
+    ref_gx3.init_thermo(); orc.init_thermo()
+
+
+@pytest.mark.parametrize("conduct", ["MU71", "bubbly"])
+@pytest.mark.parametrize("name", list(tc.LIST_SETS))
+def test_thermo_vertical_extreme_sets_bit_exact(ref_gx3, orc, name, conduct):
+    """The sets of tests/thermo_case.py, which melt columns through whole layers and away and scale kh inside the solver's
+    iteration (test_thermo_branches.py counts the columns per branch): the restatement == the reference on every array,
+    melted-away columns among them."""
+    ref_gx3.init_thermo(conduct=conduct); orc.init_thermo(conduct=conduct)
+    gone = 0
+    for n, a, icells, ii, jj in tc.list_set(name):
+        a1 = {k: v.copy() for k, v in a.items()}; a2 = {k: v.copy() for k, v in a.items()}
+        l1 = ref_gx3.thermo_vertical(DT, icells, ii, jj, a1, yday=tc.YDAY)
+        l2 = orc.thermo_vertical(DT, icells, ii, jj, a2, yday=tc.YDAY)
+        assert l1 == l2 == (0, 0, 0), (name, n, l1, l2)
+        for k in a1:
+            assert np.array_equal(a1[k], a2[k]), (name, n, k)
+        gone += int(((a["aicen"] > 0) & (a1["aicen"] == 0)).sum())
+    assert gone >= tc.FLOOR
+    ref_gx3.init_thermo(); orc.init_thermo()
+
+
+@pytest.mark.parametrize("conduct", ["MU71", "bubbly"])
+@pytest.mark.parametrize("name", tc.RECIPE_SETS)
+def test_thermo_vertical_extreme_sets_known_Tsfc_bit_exact(ref_gx3, orc, name, conduct):
+    """calc_Tsfc = F on the recipe sets.  The perturbed fluxes stop the reference in a few columns; the checker alone
+    decides which leave the list (tc.known_tsfc_set), and the reference then runs the rest without a stop, to the same
+    bits."""
+    sets = tc.known_tsfc_set(orc, name, conduct)
+    ref_gx3.init_thermo(calc_Tsfc=False, conduct=conduct)
+    for n, b, icells, ii, jj, _ in sets:
+        b1 = {k: v.copy() for k, v in b.items()}; b2 = {k: v.copy() for k, v in b.items()}
+        l1 = ref_gx3.thermo_vertical(DT, icells, ii, jj, b1, yday=tc.YDAY)
+        l2 = orc.thermo_vertical(DT, icells, ii, jj, b2, yday=tc.YDAY)
+        assert l1 == l2 == (0, 0, 0), (name, n, l1, l2)
+        for k in b1:
+            assert np.array_equal(b1[k], b2[k]), (name, n, k)
+        assert not np.array_equal(b1["eicen"], b["eicen"])
+    ref_gx3.init_thermo(); orc.init_thermo()
+
+
+def test_thermo_vertical_extreme_stop_names_the_same_cell(ref_gx3, orc):
+    """the lists of one recipe set with their stopping columns kept: checker and reference report the same
+    (l_stop, i, j) for every category, and at least one of them stops"""
+    sets = tc.known_tsfc_set(orc, "both", "MU71", keep_stops=True)
+    ref_gx3.init_thermo(calc_Tsfc=False, conduct="MU71")
+    stops = 0
+    for n, b, icells, ii, jj, _ in sets:
+        b1 = {k: v.copy() for k, v in b.items()}; b2 = {k: v.copy() for k, v in b.items()}
+        l1 = ref_gx3.thermo_vertical(DT, icells, ii, jj, b1, yday=tc.YDAY)
+        l2 = orc.thermo_vertical(DT, icells, ii, jj, b2, yday=tc.YDAY)
+        assert l1 == l2, (n, l1, l2)
+        stops += l1[0]
+    assert stops >= 1
     ref_gx3.init_thermo(); orc.init_thermo()
 
 
