@@ -1,0 +1,138 @@
+// The column batch: the state of every category of every local block, resident on the device, and the stages that run on
+// it (the thermodynamic half-step, the thermodynamic changes of the thickness distribution).  Also what those stages share
+// with the block-wise entries of the C-ABI: the names of a ThermoArgs' arrays, the status words, the decoding of a stop.
+#pragma once
+#include <cstring>
+#include <vector>
+
+#include "atmo.h"
+#include "common.h"
+#include "domain.h"
+#include "itd.h"
+#include "therm.h"
+
+namespace cice {
+
+// The device arrays of a ThermoArgs by name.  The values are the planes of cice_thermo_vertical's staging buffer (a field of
+// several planes is named by its first); A_OUT + k: the 15 per-category outputs, fsurfn ... snoice in ThermoArgs' order.
+enum { A_AICEN = 0, A_TRCRN = 1, A_VICEN = A_TRCRN + NTRCR, A_VSNON, A_EICEN, A_ESNON = A_EICEN + NILYR,
+       A_FLW = A_ESNON + NSLYR, A_POTT, A_QA, A_RHOA, A_FSNOW, A_FBOT, A_TBOT, A_LH, A_SH, A_FSWSFC,
+       A_FSWINT, A_FSWTHRU, A_SSW, A_ISW = A_SSW + NSLYR, A_OUT = A_ISW + NILYR, A_MLT = A_OUT + 15,
+       A_FRZ, A_END };
+// the (nx, ny[, nblocks]) fields of the thickness-distribution stage in the order they are staged
+enum { I2_AICE = 0, I2_AICE0, I2_FRAIN, I2_FRZMLT, I2_TF, I2_RSIDE, I2_FRESH, I2_FSALT, I2_FHOCN, I2_FRAZIL, I2_MELTL,
+       I2_FRZ_ONSET };
+
+// the status words (THERMO_STATUS_WORDS at `key`) before a launch: no error key, no column counted
+inline void thermo_status_reset(unsigned long long* key, hipStream_t s) {
+  CICE_HIP(hipMemsetAsync(key, 0xff, 8, s));
+  CICE_HIP(hipMemsetAsync(key + 1, 0, (THERMO_STATUS_WORDS - 1) * 8, s));
+}
+
+// The arguments of a launch on (nx, ny, ncat, nblocks): plane_of(A_...) is the device array of that name.  What is left at
+// zero is the caller's: the list (icells, indxi, indxj) or the dense mode's blk and niter.
+template <class PlaneOf>
+ThermoArgs thermo_args(const ThermoParams& tp, unsigned long long* key, int nx, int ny, int ncat, int nblocks, double dt,
+                       double yday, PlaneOf plane_of) {
+  ThermoArgs a{};
+  a.p = tp; a.nx = nx; a.ny = ny; a.ncat = ncat; a.nblocks = nblocks; a.dt = dt; a.yday = yday;
+  a.aicen = plane_of(A_AICEN); a.trcrn = plane_of(A_TRCRN); a.vicen = plane_of(A_VICEN); a.vsnon = plane_of(A_VSNON);
+  a.eicen = plane_of(A_EICEN); a.esnon = plane_of(A_ESNON); a.flw = plane_of(A_FLW); a.potT = plane_of(A_POTT);
+  a.Qa = plane_of(A_QA); a.rhoa = plane_of(A_RHOA); a.fsnow = plane_of(A_FSNOW); a.fbot = plane_of(A_FBOT);
+  a.Tbot = plane_of(A_TBOT); a.lhcoef = plane_of(A_LH); a.shcoef = plane_of(A_SH); a.fswsfc = plane_of(A_FSWSFC);
+  a.fswint = plane_of(A_FSWINT); a.fswthrun = plane_of(A_FSWTHRU); a.Sswabs = plane_of(A_SSW); a.Iswabs = plane_of(A_ISW);
+  double** outs[15] = {&a.fsurfn, &a.fcondtopn, &a.fsensn, &a.flatn, &a.fswabsn, &a.flwoutn, &a.evapn,
+                       &a.freshn, &a.fsaltn, &a.fhocnn, &a.meltt, &a.melts, &a.meltb, &a.congel,
+                       &a.snoice};
+  for (int k = 0; k < 15; ++k) *outs[k] = plane_of(A_OUT + k);
+  a.mlt_onset = plane_of(A_MLT); a.frz_onset = plane_of(A_FRZ);
+  a.errkey = key; a.nupdates = key + THERMO_COUNT_STRIDE;
+  return a;
+}
+
+// number of columns updated: the sum of the kernel's counters (therm.h)
+inline long long status_count(const unsigned long long* h) {
+  long long n = 0;
+  for (int k = 0; k < THERMO_COUNT_SLOTS; ++k) n += (long long)h[THERMO_COUNT_STRIDE * (1 + k)];
+  return n;
+}
+
+// "no stop": what every entry with the reference's l_stop / istop / jstop reports first
+inline void clear_stop(int32_t* l_stop, int32_t* istop, int32_t* jstop) { *l_stop = 0; *istop = 0; *jstop = 0; }
+
+// the error key of a thermo launch as the reference's stop: the cell (of the list, or of the dense plane), category, block
+void decode_err(unsigned long long key, int nx, int ncat, const int32_t* indxi, const int32_t* indxj, int32_t* l_stop,
+                int32_t* istop, int32_t* jstop, int32_t* nstop, int32_t* bstop);
+// the list key of the cell shift_ice names after a limited launch at boundary N (itd.h: STOPS)
+unsigned long long itd_shift_key(const unsigned long long* r, int N);
+
+class ColumnBatch {
+ public:
+  ColumnBatch() = default;
+  ~ColumnBatch();
+  // cice_thermo_batch_alloc.  dom: the context's domain or nullptr; its owned rows become the block table if its shape is
+  // this one, and nothing of it is kept.  A call with the shape of the last one keeps every buffer (niter, perm included).
+  void alloc(hipStream_t stream, CopyFan& fan, int nx, int ny, int nb, const Domain* dom);
+  bool allocated() const { return nb_ > 0; }
+  bool same_layout(const Domain& d) const { return nx_ == d.nx_block && ny_ == d.ny_block && nb_ == d.nblocks(); }
+  const double* aicen() const { return aicen_.p; }
+  const double* vicen() const { return vicen_.p; }
+  const double* vsnon() const { return vsnon_.p; }
+  // The entries of include/cice4_amd.h of the same names, behind their argument checks.  tp / ip: the parameters of
+  // cice_thermo_init / cice_itd_init, nullptr before that call.
+  void upload(const ThermoParams* tp, const cice_thermo_fields* h);
+  void step(const ThermoParams* tp, double dt, double yday, long long* n_updates, int32_t* l_stop, int32_t* istop,
+            int32_t* jstop, int32_t* nstop, int32_t* bstop, float* elapsed_ms);
+  void download(const ThermoParams* tp, cice_thermo_fields* h);
+  void merge(const cice_merge_fields* f);
+  void step_therm1(const ThermoParams* tp, double chio, double dt, double yday, cice_thermo_fields* st,
+                   const cice_frzmlt_fields* fz, const cice_merge_fields* mg, const cice_atmo_fields* atm,
+                   long long* n_updates, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* nstop, int32_t* bstop);
+  void step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, double dt, double yday, const cice_therm2_fields* f,
+                       int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
+  void set_option(const char* key, int value);      // before or after alloc; kept across re-allocations
+  void itd_times(bool enable, float ms[4]);         // likewise
+  // "thermo_niter", one byte per (cell, category); "thermo_perm", the permutation of the last sorted step as int32 -- either
+  // packed in 8-byte words.  Returns their number, -1 for another name.
+  long long debug_read(const char* what, long long* out, long long cap) const;
+
+ private:
+  // One field of cice_thermo_fields: its name, where it lives on the device (plane `k` of `d` in units of the field's own
+  // size), its host array, doubles per cell and block, and which way it travels.
+  enum { F_UP = 1, F_DOWN = 2, F_IO = 3, F_FLUX_UP = 4 };
+  struct Field { int name; DevBuf<double>* d; int k; const double* h; size_t per; int dir; };
+  std::vector<Field> fields(const cice_thermo_fields* h);
+  hipStream_t cs() { return fan_->forked ? fan_->next() : stream_; }   // the stream for the next host <-> device copy
+  void tracer_copy(int it, const double* from, double* to, hipMemcpyKind kind);
+  void upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef);
+  void download_fields(const ThermoParams* tp, cice_thermo_fields* h);
+  void launch_step(const ThermoParams& tp, double dt, double yday, unsigned long long status[THERMO_STATUS_WORDS],
+                   float* elapsed_ms, hipEvent_t* ev);
+  enum { MRG_UP = 1, MRG_RUN = 2, MRG_DOWN = 4, MRG_ALL = 7 };
+  void merge_phases(const cice_merge_fields* f, const double* aicen_init_dev, bool atmo_on_device, int phases);
+  void read_rec(unsigned long long h[ITD_REC_WORDS]);
+
+  hipStream_t stream_ = nullptr;
+  CopyFan* fan_ = nullptr;
+  int nx_ = 0, ny_ = 0, nb_ = 0;
+  DevBuf<int32_t> blk_;
+  std::vector<int32_t> hblk_;                // ilo, ihi, jlo, jhi per block (host copy of blk_)
+  DevBuf<double> aicen_, trcrn_, vicen_, vsnon_, eicen_, esnon_, flw_, potT_, Qa_, rhoa_, fsnow_, fbot_, Tbot_, lhcoef_,
+      shcoef_, fswsfc_, fswint_, fswthrun_, Sswabs_, Iswabs_, out15_, mlt_onset_, frz_onset_;
+  DevBuf<double> mrg_in_, mrg_acc_, fz_in_;  // merge_fluxes inputs / accumulators, frzmlt inputs + rside
+  DevBuf<double> atm_in_;                    // uatm, vatm, wind, zlvl, strax, stray (cice_step_therm1_abl)
+  DevBuf<unsigned long long> key_;           // THERMO_STATUS_WORDS: [0] error key, then the update counters (therm.h)
+  DevBuf<int32_t> perm_;                     // columns of every chunk sorted by expected work (k_thermo_sort)
+  int sort_chunk_ = 0, sort_group_ = 8;      // chunk 0: no sorting (k_thermo_dense) -- the default: DESIGN.md 3.3
+  DevBuf<unsigned char> niter_;              // solver iterations of every (cell, category) in the last step
+  bool kept_aicen_init_ = false;             // mrg_in_ holds the concentrations step_therm1 found (step_therm2_itd)
+  // thickness-distribution stage: its extra fields, record words, the events of itd_times
+  DevBuf<double> itd_b_;
+  DevBuf<int32_t> itd_bi_;
+  DevBuf<unsigned long long> rec_;
+  hipEvent_t itd_ev_[5] = {};
+  bool itd_timed_ = false;
+  float itd_ms_[4] = {0, 0, 0, 0};
+};
+
+}  // namespace cice

@@ -1,0 +1,477 @@
+// cice::ColumnBatch (batch.h) and the two decoders it shares with the block-wise entries.
+#include "batch.h"
+
+namespace cice {
+
+void decode_err(unsigned long long key, int nx, int ncat, const int32_t* indxi, const int32_t* indxj, int32_t* l_stop,
+                int32_t* istop, int32_t* jstop, int32_t* nstop, int32_t* bstop) {
+  clear_stop(l_stop, istop, jstop);
+  if (nstop) *nstop = 0;
+  if (bstop) *bstop = 0;
+  if (key == ~0ull) return;
+  *l_stop = 1;
+  const unsigned long long order = key & ((1ull << 40) - 1);
+  const unsigned long long cb = key >> 44;
+  if (indxi) {
+    *istop = indxi[order];
+    *jstop = indxj[order];
+  } else {
+    *jstop = (int32_t)(order / nx) + 1;
+    *istop = (int32_t)(order % nx) + 1;
+  }
+  if (nstop) *nstop = (int32_t)(cb % ncat) + 1;
+  if (bstop) *bstop = (int32_t)(cb / ncat) + 1;
+}
+
+unsigned long long itd_shift_key(const unsigned long long* r, int N) {
+  const int stale = (int)(r[ITD_REC_LASTDONOR] & 7) - N;   // 0 / 1: the donor of the last cell with donor > 0 is N / N + 1
+  for (int k = 0; k < 4; ++k) {
+    if (!r[ITD_REC_FLAG + k]) continue;
+    unsigned long long key = 0;
+    if (k < 2 && (stale == 0 || stale == 1)) key = r[(k == 0 ? ITD_REC_NEG_DA : ITD_REC_NEG_DV) + stale];
+    if (k == 2) key = r[ITD_REC_GT_DA];
+    if (k == 3) key = r[ITD_REC_GT_DV];
+    if (key) return key;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (r[ITD_REC_FLAG + k]) return r[ITD_REC_FLAG + k];
+  return 0;
+}
+
+ColumnBatch::~ColumnBatch() {
+  for (hipEvent_t e : itd_ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+// Every field of cice_thermo_fields, once, in the order the fields travel: what alloc sizes, upload and download move
+// and launch_step hands to the kernel.  The exceptions are the callers': of trcrn only the surface-temperature plane
+// travels, fbot / Tbot and lhcoef / shcoef stay behind when they are produced on the device, and the three surface
+// fluxes travel in (F_FLUX_UP, behind everything else) with calc_Tsfc = F only.
+std::vector<ColumnBatch::Field> ColumnBatch::fields(const cice_thermo_fields* h) {
+  static const cice_thermo_fields none{};
+  const cice_thermo_fields& f = h ? *h : none;
+  const size_t C = NCAT;
+  std::vector<Field> v = {
+      {A_AICEN, &aicen_, 0, f.aicen, C, F_IO}, {A_TRCRN, &trcrn_, 0, f.trcrn, C * NTRCR, F_IO},
+      {A_VICEN, &vicen_, 0, f.vicen, C, F_IO}, {A_VSNON, &vsnon_, 0, f.vsnon, C, F_IO},
+      {A_EICEN, &eicen_, 0, f.eicen, C * NILYR, F_IO}, {A_ESNON, &esnon_, 0, f.esnon, C * NSLYR, F_IO},
+      {A_FLW, &flw_, 0, f.flw, 1, F_UP}, {A_POTT, &potT_, 0, f.potT, 1, F_UP}, {A_QA, &Qa_, 0, f.Qa, 1, F_UP},
+      {A_RHOA, &rhoa_, 0, f.rhoa, 1, F_UP}, {A_FSNOW, &fsnow_, 0, f.fsnow, 1, F_UP}, {A_FBOT, &fbot_, 0, f.fbot, 1, F_UP},
+      {A_TBOT, &Tbot_, 0, f.Tbot, 1, F_UP}, {A_LH, &lhcoef_, 0, f.lhcoef, C, F_UP}, {A_SH, &shcoef_, 0, f.shcoef, C, F_UP},
+      {A_FSWSFC, &fswsfc_, 0, f.fswsfc, C, F_IO}, {A_FSWINT, &fswint_, 0, f.fswint, C, F_IO},
+      {A_FSWTHRU, &fswthrun_, 0, f.fswthrun, C, F_UP}, {A_SSW, &Sswabs_, 0, f.Sswabs, C * NSLYR, F_IO},
+      {A_ISW, &Iswabs_, 0, f.Iswabs, C * NILYR, F_IO}, {A_MLT, &mlt_onset_, 0, f.mlt_onset, 1, F_IO},
+      {A_FRZ, &frz_onset_, 0, f.frz_onset, 1, F_IO}};
+  const double* outs[15] = {f.fsurfn, f.fcondtopn, f.fsensn, f.flatn, f.fswabsn, f.flwoutn, f.evapn, f.freshn,
+                            f.fsaltn, f.fhocnn, f.meltt, f.melts, f.meltb, f.congel, f.snoice};
+  for (int k = 0; k < 15; ++k) v.push_back({A_OUT + k, &out15_, k, outs[k], C, F_DOWN | (k < 2 || k == 3 ? F_FLUX_UP : 0)});
+  return v;
+}
+
+void ColumnBatch::alloc(hipStream_t stream, CopyFan& fan, int nx, int ny, int nb, const Domain* dom) {
+  stream_ = stream; fan_ = &fan;
+  nx_ = nx; ny_ = ny; nb_ = nb;
+  kept_aicen_init_ = false;
+  const size_t np = (size_t)nx * ny, n2 = np * nb, nc = n2 * NCAT;
+  std::vector<int32_t> hb;
+  if (dom && same_layout(*dom)) {
+    for (int gid : dom->local) {
+      const Block& b = dom->all[gid];
+      hb.insert(hb.end(), {b.ilo, b.ihi, b.own_jlo, b.own_jhi});  // owned rows only
+    }
+  } else {
+    for (int b = 0; b < nb; ++b) hb.insert(hb.end(), {2, nx - 1, 2, ny - 1});
+  }
+  blk_.alloc(hb.size());
+  blk_.upload(hb.data(), stream_);
+  hblk_ = hb;
+  mrg_in_.alloc(5 * nc); mrg_acc_.alloc(20 * n2); fz_in_.alloc(7 * n2);
+  // (the order of the allocations as it has always been: the state, the fields per cell, the fields per category)
+  for (int group = 0; group < 3; ++group)
+    for (const Field& x : fields(nullptr))
+      if (x.d != &out15_ && group == (x.name < A_FLW ? 0 : x.per == 1 ? 1 : 2)) x.d->alloc(n2 * x.per);
+  out15_.alloc(nc * 15);
+  out15_.zero(stream_);
+  key_.alloc(THERMO_STATUS_WORDS);
+  CICE_HIP(hipStreamSynchronize(stream_));
+}
+
+// Plane `it` of trcrn(nx, ny, max_ntrcr, ncat, nblocks) for every (category, block), one strided copy between the caller's
+// array and the batch's; `from` and `to` are the two arrays' first elements
+void ColumnBatch::tracer_copy(int it, const double* from, double* to, hipMemcpyKind kind) {
+  const size_t np = (size_t)nx_ * ny_, o = (size_t)it * np, pitch = (size_t)NTRCR * np * 8;
+  CICE_HIP(hipMemcpy2DAsync(to + o, pitch, from + o, pitch, np * 8, (size_t)NCAT * nb_, kind, cs()));
+}
+
+void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef) {
+  const size_t n2 = (size_t)nx_ * ny_ * nb_;
+  const std::vector<Field> fs = fields(h);
+  for (const Field& x : fs) {
+    if (!(x.dir & F_UP)) continue;
+    if (!with_fbot_tbot && (x.name == A_FBOT || x.name == A_TBOT)) continue;   // produced on the device
+    if (!with_coef && (x.name == A_LH || x.name == A_SH)) continue;            // likewise (atmo_boundary_layer)
+    CICE_REQUIRE(x.h != nullptr, "cice_thermo_batch_upload: NULL field");
+    if (x.name == A_TRCRN && tp) {
+      // of trcrn(nx, ny, max_ntrcr, ncat, nblocks) the column physics reads and writes the surface temperature only:
+      // that plane of every (category, block), one strided copy (5 planes at ncat = 5 instead of 25)
+      tracer_copy(tp->nt_Tsfc - 1, x.h, trcrn_.p, hipMemcpyHostToDevice);
+      continue;
+    }
+    x.d->upload(x.h, cs());
+  }
+  for (const Field& x : fs) {
+    if (!(x.dir & F_FLUX_UP) || !tp || tp->calc_Tsfc) continue;  // surface fluxes are inputs (ice_therm_vertical.F90:213-217)
+    CICE_REQUIRE(x.h != nullptr, "cice_thermo_batch_upload: calc_Tsfc = F needs fsurfn, fcondtopn, flatn");
+    CICE_HIP(hipMemcpyAsync(x.d->p + x.k * n2 * x.per, x.h, n2 * x.per * 8, hipMemcpyHostToDevice, cs()));
+  }
+}
+
+void ColumnBatch::upload(const ThermoParams* tp, const cice_thermo_fields* h) {
+  kept_aicen_init_ = false;
+  upload_fields(tp, h, true, true);
+  CICE_HIP(hipStreamSynchronize(stream_));
+}
+
+// launches the dense kernel; the status words (error key, update counters) land in `status` once the
+// stream has been synchronised
+void ColumnBatch::launch_step(const ThermoParams& tp, double dt, double yday, unsigned long long status[THERMO_STATUS_WORDS],
+                              float* elapsed_ms, hipEvent_t* ev) {
+  hipStream_t s = stream_;
+  const size_t n2 = (size_t)nx_ * ny_ * nb_, nc = n2 * NCAT;
+  thermo_status_reset(key_.p, s);
+  const std::vector<Field> fs = fields(nullptr);
+  ThermoArgs a = thermo_args(tp, key_.p, nx_, ny_, NCAT, nb_, dt, yday, [&](int name) -> double* {
+    for (const Field& x : fs)
+      if (x.name == name) return x.d->p + x.k * n2 * x.per;
+    return nullptr;
+  });
+  a.blk = blk_.p;
+  if (niter_.n != nc) {
+    niter_.alloc(nc);
+    niter_.zero(s);
+  }
+  a.niter = niter_.p;
+  if (elapsed_ms) {
+    CICE_HIP(hipEventCreate(&ev[0]));
+    CICE_HIP(hipEventCreate(&ev[1]));
+    CICE_HIP(hipEventRecord(ev[0], s));
+  }
+  static const int env_chunk = [] { const char* e = std::getenv("CICE4_AMD_THERMO_SORT"); return e ? std::atoi(e) : -1; }();
+  const int chunk = env_chunk >= 0 ? env_chunk : sort_chunk_;
+  static const int env_group = [] { const char* e = std::getenv("CICE4_AMD_THERMO_GROUP"); return e ? std::atoi(e) : -1; }();
+  const int group = env_group > 0 ? env_group : sort_group_;
+  if (chunk >= 256 && chunk <= 2048 && chunk % 256 == 0 && (group == 1 || group == 2 || group == 4 || group == 8 ||
+                                                            group == 16 || group == 32)) {
+    const size_t np = (size_t)nx_ * ny_;
+    const size_t want = thermo_sorted_plane(np, chunk) * nb_ * NCAT;
+    if (perm_.n != want) perm_.alloc(want);
+    // the Tsfc tracer plane of (category, block) cb: trcrn is (nx, ny, max_ntrcr, ncat, nb)
+    thermo_launch_sorted(a, chunk, group, perm_.p, trcrn_.p + (size_t)(tp.nt_Tsfc - 1) * np, (size_t)NTRCR * np, s);
+  } else {
+    thermo_launch_dense(a, s);
+  }
+  if (elapsed_ms) CICE_HIP(hipEventRecord(ev[1], s));
+  CICE_HIP(hipMemcpyAsync(status, key_.p, THERMO_STATUS_WORDS * 8, hipMemcpyDeviceToHost, s));
+}
+
+void ColumnBatch::set_option(const char* key, int value) {
+  if (!std::strcmp(key, "sort_chunk")) {
+    CICE_REQUIRE(value == 0 || (value >= 256 && value <= 2048 && value % 256 == 0), "sort_chunk must be 0 or 256 .. 2048 in steps of 256");
+    sort_chunk_ = value;
+  } else if (!std::strcmp(key, "sort_group")) {
+    CICE_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8 || value == 16 || value == 32, "sort_group must be 1, 2, 4, 8, 16 or 32");
+    sort_group_ = value;
+  } else {
+    throw Error{CICE_EINVAL, std::string("unknown option ") + key};
+  }
+}
+
+void ColumnBatch::step(const ThermoParams* tp, double dt, double yday, long long* n_updates, int32_t* l_stop, int32_t* istop,
+                       int32_t* jstop, int32_t* nstop, int32_t* bstop, float* elapsed_ms) {
+  CICE_REQUIRE(tp, "cice_thermo_init has not been called");
+  unsigned long long h[THERMO_STATUS_WORDS];
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  launch_step(*tp, dt, yday, h, elapsed_ms, ev);
+  CICE_HIP(hipStreamSynchronize(stream_));
+  if (elapsed_ms) {
+    CICE_HIP(hipEventElapsedTime(elapsed_ms, ev[0], ev[1]));
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+  }
+  if (n_updates) *n_updates = status_count(h);
+  decode_err(h[0], nx_, NCAT, nullptr, nullptr, l_stop, istop, jstop, nstop, bstop);
+}
+
+void ColumnBatch::download_fields(const ThermoParams* tp, cice_thermo_fields* h) {
+  const size_t n2 = (size_t)nx_ * ny_ * nb_;
+  for (const Field& x : fields(h)) {
+    if (!(x.dir & F_DOWN) || !x.h) continue;
+    double* to = const_cast<double*>(x.h);   // (the fields that travel back are the struct's non-const members)
+    if (x.name == A_TRCRN && tp)             // the surface-temperature plane, as it was uploaded
+      tracer_copy(tp->nt_Tsfc - 1, trcrn_.p, to, hipMemcpyDeviceToHost);
+    else
+      CICE_HIP(hipMemcpyAsync(to, x.d->p + x.k * n2 * x.per, n2 * x.per * 8, hipMemcpyDeviceToHost, cs()));
+  }
+}
+
+void ColumnBatch::download(const ThermoParams* tp, cice_thermo_fields* h) {
+  download_fields(tp, h);
+  CICE_HIP(hipStreamSynchronize(stream_));
+}
+
+// aicen_init_dev: device copy of the initial concentrations (step_therm1 keeps one); otherwise f->aicen_init is uploaded
+// phases: the uploads, the kernel and the downloads can be asked for separately (step_therm1 puts its copies on
+// side streams and the uploads in front of every kernel)
+void ColumnBatch::merge_phases(const cice_merge_fields* f, const double* aicen_init_dev, bool atmo_on_device, int phases) {
+  hipStream_t s = stream_;
+  const size_t n2 = (size_t)nx_ * ny_ * nb_, nc = n2 * NCAT;
+  DevBuf<double>&up = mrg_in_, &acc = mrg_acc_;
+  const double* hin[5] = {f->aicen_init, f->strairxn, f->strairyn, f->Trefn, f->Qrefn};
+  for (int k = 0; k < 5 && (phases & MRG_UP); ++k) {
+    if (k == 0 && aicen_init_dev) continue;
+    if (k > 0 && atmo_on_device) continue;    // strairxn, strairyn, Trefn, Qrefn were produced in place
+    CICE_REQUIRE(hin[k] != nullptr, "cice_thermo_batch_merge: NULL input");
+    CICE_HIP(hipMemcpyAsync(up.p + (size_t)k * nc, hin[k], nc * 8, hipMemcpyHostToDevice, cs()));
+  }
+  for (int k = 0; k < 20 && (phases & MRG_UP); ++k) {
+    CICE_REQUIRE(f->acc[k] != nullptr, "cice_thermo_batch_merge: NULL accumulator");
+    CICE_HIP(hipMemcpyAsync(acc.p + (size_t)k * n2, f->acc[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  }
+  MergeArgs a{};
+  a.nx = nx_; a.ny = ny_; a.ncat = NCAT; a.nblocks = nb_; a.blk = blk_.p;
+  a.aicen_init = aicen_init_dev ? aicen_init_dev : up.p; a.flw = flw_.p;
+  auto out = [&](int k) { return (const double*)(out15_.p + (size_t)k * nc); };
+  // out15 order: fsurfn fcondtopn fsensn flatn fswabsn flwoutn evapn freshn fsaltn fhocnn meltt melts
+  //              meltb congel snoice
+  const double* src[20] = {up.p + nc, up.p + 2 * nc, out(0), out(1), out(2), out(3), out(4), out(5),
+                           out(6), up.p + 3 * nc, up.p + 4 * nc, out(7), out(8), out(9), fswthrun_.p,
+                           out(10), out(12), out(11), out(13), out(14)};
+  for (int k = 0; k < 20; ++k) {
+    a.src[k] = src[k];
+    a.acc[k] = acc.p + (size_t)k * n2;
+  }
+  if (phases & MRG_RUN) merge_launch(a, s);
+  for (int k = 0; k < 20 && (phases & MRG_DOWN); ++k)
+    CICE_HIP(hipMemcpyAsync(f->acc[k], acc.p + (size_t)k * n2, n2 * 8, hipMemcpyDeviceToHost, cs()));
+}
+
+void ColumnBatch::merge(const cice_merge_fields* f) {
+  merge_phases(f, nullptr, false, MRG_ALL);
+  CICE_HIP(hipStreamSynchronize(stream_));
+}
+
+// One call for the thermodynamic half of a time step on all local blocks (the work of step_therm1,
+// drivers/cice4/CICE_RunMod.F90:260-598; atmo_boundary_layer too where `atm` is given, else its per-category outputs
+// are inputs here): ONE upload, frzmlt_bottom_lateral (:363) -> thermo_vertical for every category (:502) ->
+// merge_fluxes (:565) on the device, ONE download, one synchronisation.
+void ColumnBatch::step_therm1(const ThermoParams* tp, double chio, double dt, double yday, cice_thermo_fields* st,
+                              const cice_frzmlt_fields* fz, const cice_merge_fields* mg, const cice_atmo_fields* atm,
+                              long long* n_updates, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* nstop,
+                              int32_t* bstop) {
+  CICE_REQUIRE(tp, "cice_thermo_init has not been called");
+  CICE_REQUIRE(st && fz && mg && l_stop && istop && jstop, "NULL argument");
+  CICE_REQUIRE(fz->aice && fz->frzmlt && fz->sst && fz->Tf && fz->strocnxT && fz->strocnyT, "NULL frzmlt input");
+  hipStream_t s = stream_;
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  // every upload first, spread over the side streams (about 150 separate host arrays), then the kernels
+  fan_->fork(s);
+  upload_fields(tp, st, false, atm == nullptr);
+  if (atm) {
+    CICE_REQUIRE(atm->uatm && atm->vatm && atm->wind && atm->zlvl, "NULL atmosphere input");
+    CICE_REQUIRE(atm->calc_strair || (atm->strax && atm->stray), "calc_strair = F needs strax, stray");
+    if (atm_in_.n < 6 * n2) atm_in_.alloc(6 * n2);
+    const double* ain[6] = {atm->uatm, atm->vatm, atm->wind, atm->zlvl, atm->strax, atm->stray};
+    for (int k = 0; k < (atm->calc_strair ? 4 : 6); ++k)
+      CICE_HIP(hipMemcpyAsync(atm_in_.p + (size_t)k * n2, ain[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  }
+  {
+    const double* fin[6] = {fz->aice, fz->frzmlt, fz->sst, fz->Tf, fz->strocnxT, fz->strocnyT};
+    for (int k = 0; k < 6; ++k)
+      CICE_HIP(hipMemcpyAsync(fz_in_.p + (size_t)k * n2, fin[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  }
+  merge_phases(mg, mrg_in_.p, atm != nullptr, MRG_UP);
+  fan_->join();
+  if (atm) {   // atmo_boundary_layer for every category (CICE_RunMod.F90:402-425), on the state before the update
+    AtmoArgs a{};
+    a.p.init();
+    a.nx = nx_; a.ny = ny_; a.ncat = NCAT; a.nblocks = nb_; a.ocn = 0; a.calc_strair = atm->calc_strair != 0;
+    a.blk = blk_.p; a.aicen = aicen_.p; a.Tsf = trcrn_.p; a.it_Tsfc = tp->nt_Tsfc - 1;
+    a.potT = potT_.p; a.Qa = Qa_.p; a.rhoa = rhoa_.p;
+    a.uatm = atm_in_.p; a.vatm = atm_in_.p + n2; a.wind = atm_in_.p + 2 * n2; a.zlvl = atm_in_.p + 3 * n2;
+    a.strax = atm_in_.p + 4 * n2; a.stray = atm_in_.p + 5 * n2;
+    a.strx = mrg_in_.p + nc; a.stry = mrg_in_.p + 2 * nc; a.Tref = mrg_in_.p + 3 * nc; a.Qref = mrg_in_.p + 4 * nc;
+    a.lhcoef = lhcoef_.p; a.shcoef = shcoef_.p;
+    atmo_launch_dense(a, s);
+  }
+  for (int b = 0; b < nb_; ++b) {   // frzmlt_bottom_lateral per block, on the uploaded enthalpies
+    FrzmltArgs a{};
+    a.nx = nx_; a.ny = ny_; a.dt = dt; a.ustar_min = tp->ustar_min; a.chio = chio;
+    a.ilo = hblk_[4 * b]; a.ihi = hblk_[4 * b + 1]; a.jlo = hblk_[4 * b + 2]; a.jhi = hblk_[4 * b + 3];
+    const size_t o = (size_t)b * np;
+    a.aice = fz_in_.p + o; a.frzmlt = fz_in_.p + n2 + o; a.sst = fz_in_.p + 2 * n2 + o;
+    a.Tf = fz_in_.p + 3 * n2 + o; a.strocnxT = fz_in_.p + 4 * n2 + o; a.strocnyT = fz_in_.p + 5 * n2 + o;
+    a.Tbot = Tbot_.p + o; a.fbot = fbot_.p + o; a.rside = fz_in_.p + 6 * n2 + o;
+    a.eicen = eicen_.p + (size_t)b * NCAT * NILYR * np; a.esnon = esnon_.p + (size_t)b * NCAT * NSLYR * np;
+    frzmlt_launch(a, s);
+  }
+  // aicen_init of merge_fluxes = the concentrations before the column update (CICE_RunMod.F90:342-355)
+  CICE_HIP(hipMemcpyAsync(mrg_in_.p, aicen_.p, nc * 8, hipMemcpyDeviceToDevice, s));
+  kept_aicen_init_ = true;
+  unsigned long long h[THERMO_STATUS_WORDS];
+  launch_step(*tp, dt, yday, h, nullptr, nullptr);
+  merge_phases(mg, mrg_in_.p, atm != nullptr, MRG_RUN);
+  fan_->fork(s);   // ... and every download after the last kernel
+  merge_phases(mg, mrg_in_.p, atm != nullptr, MRG_DOWN);
+  download_fields(tp, st);
+  if (atm) {
+    double* aout[6] = {atm->strairxn, atm->strairyn, atm->Trefn, atm->Qrefn, atm->lhcoef, atm->shcoef};
+    const double* asrc[6] = {mrg_in_.p + nc, mrg_in_.p + 2 * nc, mrg_in_.p + 3 * nc, mrg_in_.p + 4 * nc,
+                             lhcoef_.p, shcoef_.p};
+    for (int k = 0; k < 6; ++k)
+      if (aout[k]) CICE_HIP(hipMemcpyAsync(aout[k], asrc[k], nc * 8, hipMemcpyDeviceToHost, cs()));
+  }
+  if (fz->Tbot) Tbot_.download(fz->Tbot, cs());
+  if (fz->fbot) fbot_.download(fz->fbot, cs());
+  if (fz->rside) CICE_HIP(hipMemcpyAsync(fz->rside, fz_in_.p + 6 * n2, n2 * 8, hipMemcpyDeviceToHost, cs()));
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  if (n_updates) *n_updates = status_count(h);
+  decode_err(h[0], nx_, NCAT, nullptr, nullptr, l_stop, istop, jstop, nstop, bstop);
+}
+
+// the record words once the stream has run dry
+void ColumnBatch::read_rec(unsigned long long h[ITD_REC_WORDS]) {
+  CICE_HIP(hipMemcpyAsync(h, rec_.p, ITD_REC_WORDS * 8, hipMemcpyDeviceToHost, stream_));
+  CICE_HIP(hipStreamSynchronize(stream_));
+}
+
+// The thickness-distribution stage on the batch (ice_step_mod.F90:286-422): see include/cice4_amd.h
+void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, double dt, double yday,
+                                  const cice_therm2_fields* f, int32_t* l_stop, int32_t* istop, int32_t* jstop,
+                                  int32_t* bstop, int32_t* stage) {
+  CICE_REQUIRE(ip, "cice_itd_init has not been called");
+  CICE_REQUIRE(dt > 0.0, "dt");
+  CICE_REQUIRE(f->aicen && f->trcrn && f->vicen && f->vsnon && f->eicen && f->esnon && f->vicen_init && f->frain &&
+                   f->frzmlt && f->Tf && f->rside && f->tmask && f->aice && f->aice0 && f->fresh && f->fsalt && f->fhocn &&
+                   f->frazil && f->meltl && f->frz_onset, "cice_step_therm2_itd: NULL field");
+  const bool resident = f->state_resident != 0;
+  CICE_REQUIRE(resident || f->aicen_init, "cice_step_therm2_itd: aicen_init is needed without a resident state");
+  CICE_REQUIRE(!resident || (tp && tp->nt_Tsfc - 1 == ip->it_Tsfc),
+               "cice_step_therm2_itd: state_resident needs cice_thermo_init with the same nt_Tsfc");
+  CICE_REQUIRE(f->aicen_init || kept_aicen_init_,
+               "cice_step_therm2_itd: aicen_init = NULL needs a cice_step_therm1 call on this batch in front");
+  hipStream_t s = stream_;
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  if (itd_b_.n < 2 * nc + 12 * n2) itd_b_.alloc(2 * nc + 12 * n2);
+  if (itd_bi_.n < n2 + (size_t)nb_) itd_bi_.alloc(n2 + (size_t)nb_);
+  rec_.alloc(ITD_REC_WORDS);
+  const bool timed = itd_timed_;
+  for (hipEvent_t& e : itd_ev_)
+    if (timed && !e) CICE_HIP(hipEventCreate(&e));
+  double* ainit = itd_b_.p;
+  double* vinit = itd_b_.p + nc;
+  double* d2 = itd_b_.p + 2 * nc;
+  int32_t* flag = itd_bi_.p + n2;
+  const int ntr = ip->ntrcr, it_T = ip->it_Tsfc;
+  auto upload = [&](bool state) {
+    fan_->fork(s);
+    if (state) {
+      aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
+      eicen_.upload(f->eicen, cs()); esnon_.upload(f->esnon, cs());
+    }
+    for (int it = 0; it < ntr; ++it)
+      if (state || it != it_T) tracer_copy(it, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
+    if (f->aicen_init) CICE_HIP(hipMemcpyAsync(ainit, f->aicen_init, nc * 8, hipMemcpyHostToDevice, cs()));
+    CICE_HIP(hipMemcpyAsync(vinit, f->vicen_init, nc * 8, hipMemcpyHostToDevice, cs()));
+    const double* in2[12] = {f->aice, f->aice0, f->frain, f->frzmlt, f->Tf, f->rside, f->fresh, f->fsalt, f->fhocn,
+                             nullptr, f->meltl, f->frz_onset};
+    for (int k = 0; k < 12; ++k)
+      if (in2[k]) CICE_HIP(hipMemcpyAsync(d2 + (size_t)k * n2, in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+    CICE_HIP(hipMemcpyAsync(itd_bi_.p, f->tmask, n2 * 4, hipMemcpyHostToDevice, cs()));
+    fan_->join();
+    CICE_HIP(hipMemsetAsync(d2 + (size_t)I2_FRAZIL * n2, 0, n2 * 8, s));
+    CICE_HIP(hipMemsetAsync(rec_.p, 0, ITD_REC_WORDS * 8, s));
+    CICE_HIP(hipMemsetAsync(flag, 0, (size_t)nb_ * 4, s));
+  };
+  ItdArgs a{};
+  a.p = *ip;
+  a.nx = nx_; a.ny = ny_; a.nblocks = nb_; a.blk = blk_.p; a.kitd = f->kitd != 0; a.dt = dt; a.yday = yday;
+  a.blockflag = flag; a.blockflag_out = flag; a.tmask = itd_bi_.p;
+  a.aicen = aicen_.p; a.trcrn = trcrn_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.eicen = eicen_.p;
+  a.esnon = esnon_.p; a.vicen_init = vinit;
+  a.aicen_init = f->aicen_init ? ainit : mrg_in_.p;   // NULL: the concentrations step_therm1 kept for merge_fluxes
+  a.aice = d2 + I2_AICE * n2; a.aice0 = d2 + I2_AICE0 * n2; a.frain = d2 + I2_FRAIN * n2; a.frzmlt = d2 + I2_FRZMLT * n2;
+  a.Tf = d2 + I2_TF * n2; a.rside = d2 + I2_RSIDE * n2; a.fresh = d2 + I2_FRESH * n2; a.fsalt = d2 + I2_FSALT * n2;
+  a.fhocn = d2 + I2_FHOCN * n2; a.frazil = d2 + I2_FRAZIL * n2; a.meltl = d2 + I2_MELTL * n2;
+  a.frz_onset = d2 + I2_FRZ_ONSET * n2;
+  a.rec = rec_.p;
+  auto run = [&](int bfail, int nlimit, int bend_add, int bend_melt) {
+    ItdArgs k = a;
+    k.bfail = bfail; k.nlimit = nlimit;
+    if (timed) CICE_HIP(hipEventRecord(itd_ev_[0], s));
+    itd_launch_rain_aggregate(k, s);
+    if (timed) CICE_HIP(hipEventRecord(itd_ev_[1], s));
+    if (k.kitd) itd_launch_linear(k, s);
+    if (timed) CICE_HIP(hipEventRecord(itd_ev_[2], s));
+    k.bend = bend_add;
+    itd_launch_add_new_ice(k, s);
+    if (timed) CICE_HIP(hipEventRecord(itd_ev_[3], s));
+    k.bend = bend_melt;
+    itd_launch_lateral_melt(k, s);
+    if (timed) CICE_HIP(hipEventRecord(itd_ev_[4], s));
+  };
+  unsigned long long r[ITD_REC_WORDS];
+  upload(!resident);
+  run(nb_, 0, nb_, nb_);
+  read_rec(r);
+  for (int k = 0; k < 4 && timed; ++k) CICE_HIP(hipEventElapsedTime(&itd_ms_[k], itd_ev_[k], itd_ev_[k + 1]));
+  clear_stop(l_stop, istop, jstop);
+  *bstop = 0; *stage = 0;
+  int bl = -1, N = 0, ba = -1;
+  if (r[ITD_REC_SHIFT]) {
+    const unsigned long long v = r[ITD_REC_SHIFT] - 1;
+    bl = nb_ - 1 - (int)(v >> 8);
+    N = NCAT - (int)(v & 0xff);
+  }
+  if (r[ITD_REC_ADD]) ba = nb_ - 1 - (int)(r[ITD_REC_ADD] >> 32);
+  if (bl >= 0 || ba >= 0) {            // a stop: again from the caller's arrays, up to where the reference stops (itd.h)
+    const bool in_shift = bl >= 0 && (ba < 0 || bl <= ba);
+    const int bf = in_shift ? bl : ba;
+    upload(true);
+    run(bf, in_shift ? N : 0, in_shift ? bf : bf + 1, bf);
+    read_rec(r);
+    unsigned long long key = in_shift ? itd_shift_key(r, N) : (r[ITD_REC_ADD] & 0xffffffffull);
+    *l_stop = 1; *bstop = bf + 1; *stage = in_shift ? 1 : 2;
+    if (key) { *istop = (int32_t)((key - 1) % nx_) + 1; *jstop = (int32_t)((key - 1) / nx_) + 1; }
+  }
+  fan_->fork(s);
+  aicen_.download(f->aicen, cs()); vicen_.download(f->vicen, cs()); vsnon_.download(f->vsnon, cs());
+  eicen_.download(f->eicen, cs()); esnon_.download(f->esnon, cs());
+  for (int it = 0; it < ntr; ++it) tracer_copy(it, trcrn_.p, f->trcrn, hipMemcpyDeviceToHost);
+  double* out2[12] = {f->aice, f->aice0, nullptr, nullptr, nullptr, nullptr, f->fresh, f->fsalt, f->fhocn, f->frazil,
+                      f->meltl, f->frz_onset};
+  for (int k = 0; k < 12; ++k)
+    if (out2[k]) CICE_HIP(hipMemcpyAsync(out2[k], d2 + (size_t)k * n2, n2 * 8, hipMemcpyDeviceToHost, cs()));
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+}
+
+void ColumnBatch::itd_times(bool enable, float ms[4]) {
+  itd_timed_ = enable;
+  for (int k = 0; k < 4 && ms; ++k) ms[k] = itd_ms_[k];
+}
+
+long long ColumnBatch::debug_read(const char* what, long long* out, long long cap) const {
+  const bool niter = !std::strcmp(what, "thermo_niter");
+  if (!niter && std::strcmp(what, "thermo_perm")) return -1;
+  const void* src = niter ? (const void*)niter_.p : (const void*)perm_.p;
+  const long long nbytes = niter ? (long long)niter_.n : (long long)perm_.n * 4, nw = (nbytes + 7) / 8;
+  if (out && nbytes) {
+    CICE_REQUIRE(cap >= nw, "cice_evp_debug: buffer too small");
+    CICE_HIP(hipStreamSynchronize(stream_));
+    CICE_HIP(hipMemcpy(out, src, (size_t)nbytes, hipMemcpyDeviceToHost));
+  }
+  return nw;
+}
+
+}  // namespace cice

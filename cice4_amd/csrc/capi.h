@@ -20,6 +20,7 @@
 #include "therm.h"
 #include "itd.h"
 #include "transport.h"
+#include "batch.h"
 
 using namespace cice;
 
@@ -95,31 +96,17 @@ struct cice_ctx {
   // thermo
   ThermoParams tp{};
   bool have_thermo = false;
-  DevBuf<unsigned long long> tkey;  // THERMO_STATUS_WORDS: [0] error key, then the update counters (therm.h)
-  // batched thermo state
-  struct Batch {
-    int nx = 0, ny = 0, nb = 0;
-    DevBuf<int32_t> blk;
-    DevBuf<double> aicen, trcrn, vicen, vsnon, eicen, esnon, flw, potT, Qa, rhoa, fsnow, fbot, Tbot,
-        lhcoef, shcoef, fswsfc, fswint, fswthrun, Sswabs, Iswabs, out15, mlt_onset, frz_onset;
-    DevBuf<double> mrg_in, mrg_acc, fz_in;   // merge_fluxes inputs / accumulators, frzmlt inputs + rside
-    DevBuf<int32_t> perm;                    // columns of every chunk sorted by expected work (k_thermo_sort)
-    int sort_chunk = 0, sort_group = 8;      // chunk 0: no sorting (k_thermo_dense) -- the default: DESIGN.md 3.3
-    DevBuf<unsigned char> niter;             // solver iterations of every (cell, category) in the last step
-    DevBuf<double> atm_in;                   // uatm, vatm, wind, zlvl, strax, stray (cice_step_therm1_abl)
-    std::vector<int32_t> hblk;               // ilo, ihi, jlo, jhi per block (host copy of blk)
-    bool kept_aicen_init = false;            // mrg_in holds the concentrations cice_step_therm1 found (cice_step_therm2_itd)
-  } tb;
-  // thickness-distribution stage (itd.h): module variables given to cice_itd_init, staging of the block-wise entries
-  // (grown on demand), the batch's extra fields, record words, the events of cice_therm2_itd_times
+  DevBuf<unsigned long long> tkey;  // THERMO_STATUS_WORDS of the block-wise entries: [0] error key, then the update counters
+  ColumnBatch batch;           // the device-resident state of all local blocks and its stages (batch.h)
+  const ThermoParams* thermo() const { return have_thermo ? &tp : nullptr; }   // what the batch's methods are handed:
+  const ItdParams* itd() const { return have_itd ? &ip : nullptr; }            // nullptr before the init call
+  // thickness-distribution stage (itd.h): module variables given to cice_itd_init, staging and record words of the
+  // block-wise entries (grown on demand)
   ItdParams ip{};
   bool have_itd = false;
-  DevBuf<double> itd_d, itd_b;
-  DevBuf<int32_t> itd_i, itd_bi;
+  DevBuf<double> itd_d;
+  DevBuf<int32_t> itd_i;
   DevBuf<unsigned long long> itd_rec;
-  hipEvent_t itd_ev[5] = {};
-  bool itd_timed = false;                  // cice_therm2_itd_times(enable): events around the stage's kernels
-  float itd_ms[4] = {0, 0, 0, 0};
   // device is required lazily: domain queries work on a CPU-only host
   // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
   // process may have changed the current device since the last call (another context on another GPU,
@@ -156,9 +143,6 @@ struct cice_ctx {
   }                                                           \
   return CICE_OK;
 
-// "no stop": what every entry with the reference's l_stop / istop / jstop reports first
-inline void clear_stop(int32_t* l_stop, int32_t* istop, int32_t* jstop) { *l_stop = 0; *istop = 0; *jstop = 0; }
-
-// Plane `it` of trcrn(nx, ny, max_ntrcr, ncat, nblocks) for every (category, block) of the thermodynamic batch, one strided
-// copy between the caller's array and the batch's (capi_thermo.hip); `from` and `to` are the two arrays' first elements
-void batch_tracer_copy(cice_ctx* c, int it, const double* from, double* to, hipMemcpyKind kind);
+#define NEED_EVP CICE_REQUIRE(c_->evp != nullptr, "cice_evp_init has not been called")
+// (`also`: a pointer the entry has always checked in the same breath)
+#define NEED_BATCH(also) CICE_REQUIRE(c_->batch.allocated() && (also), "cice_thermo_batch_alloc has not been called")

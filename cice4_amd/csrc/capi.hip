@@ -168,8 +168,6 @@ int cice_destroy(cice_ctx* ctx) {
   if (!ctx) return CICE_EINVAL;
   ctx->frame_host.release();
   ctx->tv_host.release();
-  for (hipEvent_t e : ctx->itd_ev)
-    if (e) (void)hipEventDestroy(e);
   ctx->unpin_all();
   ctx->evp.reset();
   ctx->transport.reset();

@@ -13,8 +13,6 @@ int cice_evp_init(cice_ctx* ctx, const cice_evp_config* cfg, const cice_evp_grid
   CICE_CATCH
 }
 
-#define NEED_EVP CICE_REQUIRE(c_->evp != nullptr, "cice_evp_init has not been called")
-
 int cice_evp_upload(cice_ctx* ctx, const cice_evp_fields* f) {
   CICE_TRY(ctx) c_->chain_ready = false; NEED_EVP; CICE_REQUIRE(f, "NULL argument"); c_->evp->upload(*f); CICE_CATCH
 }
@@ -42,11 +40,10 @@ int cice_evp(cice_ctx* ctx, double dt, cice_evp_fields* f) {
 int cice_evp_adopt_thermo_state(cice_ctx* ctx) {
   CICE_TRY(ctx) c_->chain_ready = false;
   NEED_EVP;
-  auto& t = c_->tb;
-  CICE_REQUIRE(t.nb > 0, "cice_thermo_batch_alloc has not been called");
-  CICE_REQUIRE(t.nx == c_->dom.nx_block && t.ny == c_->dom.ny_block && t.nb == c_->dom.nblocks(),
+  NEED_BATCH(true);
+  CICE_REQUIRE(c_->batch.same_layout(c_->dom),
                "cice_evp_adopt_thermo_state: the thermodynamic batch has another block layout than the dynamics");
-  c_->evp->adopt_state(t.aicen.p, t.vicen.p, t.vsnon.p);
+  c_->evp->adopt_state(c_->batch.aicen(), c_->batch.vicen(), c_->batch.vsnon());
   CICE_CATCH
 }
 int cice_evp_pin_fields(cice_ctx* ctx, const cice_evp_fields* f) {
@@ -191,17 +188,8 @@ int cice_evp_peer_connect_ipc(cice_ctx* ctx, int side, const char handles[3][64]
 int cice_evp_debug(cice_ctx* ctx, const char* what, long long* out, long long* count) {
   CICE_TRY(ctx)
   CICE_REQUIRE(what && count, "NULL argument");
-  // of the batched thermo state: "thermo_niter", one byte per (cell, category); "thermo_perm", the permutation of the last
-  // sorted step as int32 -- either packed in the words
-  const bool niter = !std::strcmp(what, "thermo_niter");
-  if (niter || !std::strcmp(what, "thermo_perm")) {
-    const void* src = niter ? (const void*)c_->tb.niter.p : (const void*)c_->tb.perm.p;
-    const long long nbytes = niter ? (long long)c_->tb.niter.n : (long long)c_->tb.perm.n * 4, nw = (nbytes + 7) / 8;
-    if (out && nbytes) {
-      CICE_REQUIRE(*count >= nw, "cice_evp_debug: buffer too small");
-      CICE_HIP(hipStreamSynchronize(c_->stream));
-      CICE_HIP(hipMemcpy(out, src, (size_t)nbytes, hipMemcpyDeviceToHost));
-    }
+  const long long nw = c_->batch.debug_read(what, out, *count);   // "thermo_niter", "thermo_perm": the column batch's
+  if (nw >= 0) {
     *count = nw;
     return CICE_OK;
   }

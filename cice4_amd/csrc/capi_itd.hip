@@ -5,8 +5,6 @@ namespace {
 // plane offsets of the block-wise staging buffer (units of nx*ny doubles)
 enum { IB_AICEN = 0, IB_VICEN = 5, IB_VSNON = 10, IB_TRCRN = 15, IB_EICEN = 40, IB_ESNON = 60, IB_AINIT = 65,
        IB_VINIT = 70, IB_2D = 75, IB_SHIFT = 87, IB_PLANES = 102 };
-enum { I2_AICE = 0, I2_AICE0, I2_FRAIN, I2_FRZMLT, I2_TF, I2_RSIDE, I2_FRESH, I2_FSALT, I2_FHOCN, I2_FRAZIL, I2_MELTL,
-       I2_FRZ_ONSET };
 static_assert(NCAT == 5 && NILYR == 4 && NSLYR == 1 && NTRCR == 5, "plane offsets above");
 
 // the record words once the stream has run dry
@@ -18,22 +16,6 @@ void itd_read_rec(cice_ctx* c, unsigned long long h[ITD_REC_WORDS]) {
 // the state arrays of the block-wise entries in the order they travel; an entry moves the members it names
 enum { ST_AICEN = 1, ST_VICEN = 2, ST_VSNON = 4, ST_TRCRN = 8, ST_EICEN = 16, ST_ESNON = 32, ST_ALL = 63 };
 struct ItdState { double *aicen, *vicen, *vsnon, *trcrn, *eicen, *esnon; };
-
-// the list key of the cell shift_ice names after a limited launch at boundary N (itd.h: STOPS)
-unsigned long long itd_shift_key(const unsigned long long* r, int N) {
-  const int stale = (int)(r[ITD_REC_LASTDONOR] & 7) - N;   // 0 / 1: the donor of the last cell with donor > 0 is N / N + 1
-  for (int k = 0; k < 4; ++k) {
-    if (!r[ITD_REC_FLAG + k]) continue;
-    unsigned long long key = 0;
-    if (k < 2 && (stale == 0 || stale == 1)) key = r[(k == 0 ? ITD_REC_NEG_DA : ITD_REC_NEG_DV) + stale];
-    if (k == 2) key = r[ITD_REC_GT_DA];
-    if (k == 3) key = r[ITD_REC_GT_DV];
-    if (key) return key;
-  }
-  for (int k = 0; k < 4; ++k)
-    if (r[ITD_REC_FLAG + k]) return r[ITD_REC_FLAG + k];
-  return 0;
-}
 
 struct ItdBlock {   // one (nx, ny) block staged on the device
   cice_ctx* c;
@@ -284,124 +266,16 @@ int cice_lateral_melt(cice_ctx* ctx, int nx, int ny, int ilo, int ihi, int jlo, 
 int cice_step_therm2_itd(cice_ctx* ctx, double dt, double yday, const cice_therm2_fields* f, int32_t* l_stop,
                          int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage) {
   CICE_TRY(ctx) c_->chain_ready = false;
-  auto& t = c_->tb;
   CICE_REQUIRE(f && l_stop && istop && jstop && bstop && stage, "NULL argument");
   if (f->ncat == 1) throw Error{CICE_EUNSUPPORTED, "cice_step_therm2_itd: ncat = 1 (reduce_area) is not built"};
   CICE_REQUIRE(f->ncat == NCAT, "cice_step_therm2_itd: ncat is not the library's");
-  CICE_REQUIRE(t.nb > 0, "cice_thermo_batch_alloc has not been called");
-  CICE_REQUIRE(c_->have_itd, "cice_itd_init has not been called");
-  CICE_REQUIRE(dt > 0.0, "dt");
-  CICE_REQUIRE(f->aicen && f->trcrn && f->vicen && f->vsnon && f->eicen && f->esnon && f->vicen_init && f->frain &&
-                   f->frzmlt && f->Tf && f->rside && f->tmask && f->aice && f->aice0 && f->fresh && f->fsalt && f->fhocn &&
-                   f->frazil && f->meltl && f->frz_onset, "cice_step_therm2_itd: NULL field");
-  const bool resident = f->state_resident != 0;
-  CICE_REQUIRE(resident || f->aicen_init, "cice_step_therm2_itd: aicen_init is needed without a resident state");
-  CICE_REQUIRE(!resident || (c_->have_thermo && c_->tp.nt_Tsfc - 1 == c_->ip.it_Tsfc),
-               "cice_step_therm2_itd: state_resident needs cice_thermo_init with the same nt_Tsfc");
-  CICE_REQUIRE(f->aicen_init || t.kept_aicen_init,
-               "cice_step_therm2_itd: aicen_init = NULL needs a cice_step_therm1 call on this batch in front");
-  hipStream_t s = c_->stream;
-  const size_t np = (size_t)t.nx * t.ny, n2 = np * t.nb, nc = n2 * NCAT;
-  if (c_->itd_b.n < 2 * nc + 12 * n2) c_->itd_b.alloc(2 * nc + 12 * n2);
-  if (c_->itd_bi.n < n2 + (size_t)t.nb) c_->itd_bi.alloc(n2 + (size_t)t.nb);
-  c_->itd_rec.alloc(ITD_REC_WORDS);
-  const bool timed = c_->itd_timed;
-  for (hipEvent_t& e : c_->itd_ev)
-    if (timed && !e) CICE_HIP(hipEventCreate(&e));
-  double* ainit = c_->itd_b.p;
-  double* vinit = c_->itd_b.p + nc;
-  double* d2 = c_->itd_b.p + 2 * nc;
-  int32_t* flag = c_->itd_bi.p + n2;
-  const int ntr = c_->ip.ntrcr, it_T = c_->ip.it_Tsfc;
-  auto upload = [&](bool state) {
-    c_->fan.fork(s);
-    if (state) {
-      t.aicen.upload(f->aicen, c_->cs()); t.vicen.upload(f->vicen, c_->cs()); t.vsnon.upload(f->vsnon, c_->cs());
-      t.eicen.upload(f->eicen, c_->cs()); t.esnon.upload(f->esnon, c_->cs());
-    }
-    for (int it = 0; it < ntr; ++it)
-      if (state || it != it_T) batch_tracer_copy(c_, it, f->trcrn, t.trcrn.p, hipMemcpyHostToDevice);
-    if (f->aicen_init) CICE_HIP(hipMemcpyAsync(ainit, f->aicen_init, nc * 8, hipMemcpyHostToDevice, c_->cs()));
-    CICE_HIP(hipMemcpyAsync(vinit, f->vicen_init, nc * 8, hipMemcpyHostToDevice, c_->cs()));
-    const double* in2[12] = {f->aice, f->aice0, f->frain, f->frzmlt, f->Tf, f->rside, f->fresh, f->fsalt, f->fhocn,
-                             nullptr, f->meltl, f->frz_onset};
-    for (int k = 0; k < 12; ++k)
-      if (in2[k]) CICE_HIP(hipMemcpyAsync(d2 + (size_t)k * n2, in2[k], n2 * 8, hipMemcpyHostToDevice, c_->cs()));
-    CICE_HIP(hipMemcpyAsync(c_->itd_bi.p, f->tmask, n2 * 4, hipMemcpyHostToDevice, c_->cs()));
-    c_->fan.join();
-    CICE_HIP(hipMemsetAsync(d2 + (size_t)I2_FRAZIL * n2, 0, n2 * 8, s));
-    CICE_HIP(hipMemsetAsync(c_->itd_rec.p, 0, ITD_REC_WORDS * 8, s));
-    CICE_HIP(hipMemsetAsync(flag, 0, (size_t)t.nb * 4, s));
-  };
-  ItdArgs a{};
-  a.p = c_->ip;
-  a.nx = t.nx; a.ny = t.ny; a.nblocks = t.nb; a.blk = t.blk.p; a.kitd = f->kitd != 0; a.dt = dt; a.yday = yday;
-  a.blockflag = flag; a.blockflag_out = flag; a.tmask = c_->itd_bi.p;
-  a.aicen = t.aicen.p; a.trcrn = t.trcrn.p; a.vicen = t.vicen.p; a.vsnon = t.vsnon.p; a.eicen = t.eicen.p;
-  a.esnon = t.esnon.p; a.vicen_init = vinit;
-  a.aicen_init = f->aicen_init ? ainit : t.mrg_in.p;   // NULL: the concentrations cice_step_therm1 kept for merge_fluxes
-  a.aice = d2 + I2_AICE * n2; a.aice0 = d2 + I2_AICE0 * n2; a.frain = d2 + I2_FRAIN * n2; a.frzmlt = d2 + I2_FRZMLT * n2;
-  a.Tf = d2 + I2_TF * n2; a.rside = d2 + I2_RSIDE * n2; a.fresh = d2 + I2_FRESH * n2; a.fsalt = d2 + I2_FSALT * n2;
-  a.fhocn = d2 + I2_FHOCN * n2; a.frazil = d2 + I2_FRAZIL * n2; a.meltl = d2 + I2_MELTL * n2;
-  a.frz_onset = d2 + I2_FRZ_ONSET * n2;
-  a.rec = c_->itd_rec.p;
-  auto run = [&](int bfail, int nlimit, int bend_add, int bend_melt) {
-    ItdArgs k = a;
-    k.bfail = bfail; k.nlimit = nlimit;
-    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[0], s));
-    itd_launch_rain_aggregate(k, s);
-    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[1], s));
-    if (k.kitd) itd_launch_linear(k, s);
-    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[2], s));
-    k.bend = bend_add;
-    itd_launch_add_new_ice(k, s);
-    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[3], s));
-    k.bend = bend_melt;
-    itd_launch_lateral_melt(k, s);
-    if (timed) CICE_HIP(hipEventRecord(c_->itd_ev[4], s));
-  };
-  unsigned long long r[ITD_REC_WORDS];
-  upload(!resident);
-  run(t.nb, 0, t.nb, t.nb);
-  itd_read_rec(c_, r);
-  for (int k = 0; k < 4 && timed; ++k) CICE_HIP(hipEventElapsedTime(&c_->itd_ms[k], c_->itd_ev[k], c_->itd_ev[k + 1]));
-  clear_stop(l_stop, istop, jstop);
-  *bstop = 0; *stage = 0;
-  int bl = -1, N = 0, ba = -1;
-  if (r[ITD_REC_SHIFT]) {
-    const unsigned long long v = r[ITD_REC_SHIFT] - 1;
-    bl = t.nb - 1 - (int)(v >> 8);
-    N = NCAT - (int)(v & 0xff);
-  }
-  if (r[ITD_REC_ADD]) ba = t.nb - 1 - (int)(r[ITD_REC_ADD] >> 32);
-  if (bl >= 0 || ba >= 0) {            // a stop: again from the caller's arrays, up to where the reference stops (itd.h)
-    const bool in_shift = bl >= 0 && (ba < 0 || bl <= ba);
-    const int bf = in_shift ? bl : ba;
-    upload(true);
-    run(bf, in_shift ? N : 0, in_shift ? bf : bf + 1, bf);
-    itd_read_rec(c_, r);
-    unsigned long long key = in_shift ? itd_shift_key(r, N) : (r[ITD_REC_ADD] & 0xffffffffull);
-    *l_stop = 1; *bstop = bf + 1; *stage = in_shift ? 1 : 2;
-    if (key) { *istop = (int32_t)((key - 1) % t.nx) + 1; *jstop = (int32_t)((key - 1) / t.nx) + 1; }
-  }
-  c_->fan.fork(s);
-  t.aicen.download(f->aicen, c_->cs()); t.vicen.download(f->vicen, c_->cs()); t.vsnon.download(f->vsnon, c_->cs());
-  t.eicen.download(f->eicen, c_->cs()); t.esnon.download(f->esnon, c_->cs());
-  for (int it = 0; it < ntr; ++it) batch_tracer_copy(c_, it, t.trcrn.p, f->trcrn, hipMemcpyDeviceToHost);
-  double* out2[12] = {f->aice, f->aice0, nullptr, nullptr, nullptr, nullptr, f->fresh, f->fsalt, f->fhocn, f->frazil,
-                      f->meltl, f->frz_onset};
-  for (int k = 0; k < 12; ++k)
-    if (out2[k]) CICE_HIP(hipMemcpyAsync(out2[k], d2 + (size_t)k * n2, n2 * 8, hipMemcpyDeviceToHost, c_->cs()));
-  c_->fan.join();
-  CICE_HIP(hipStreamSynchronize(s));
+  NEED_BATCH(true);
+  c_->batch.step_therm2_itd(c_->thermo(), c_->itd(), dt, yday, f, l_stop, istop, jstop, bstop, stage);
   CICE_CATCH
 }
 
 int cice_therm2_itd_times(cice_ctx* ctx, int enable, float ms[4]) {
-  CICE_TRY(ctx)
-  c_->itd_timed = enable != 0;
-  for (int k = 0; k < 4 && ms; ++k) ms[k] = c_->itd_ms[k];
-  CICE_CATCH
+  CICE_TRY(ctx) c_->batch.itd_times(enable != 0, ms); CICE_CATCH
 }
 
 }  // extern "C"

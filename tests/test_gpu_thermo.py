@@ -429,6 +429,71 @@ def test_sorted_columns_give_the_same_bits(ctx, chunk, group, recipe):
             assert np.array_equal(res[0][step][0][k], res[chunk][step][0][k]), (step, k)
 
 
+def test_batch_settings_hold_before_and_across_allocations():
+    """On a context of its own: the sort options and the stage's timing switch set BEFORE the first cice_thermo_batch_alloc
+    take effect, and survive re-allocations to another shape and back (the sorted step's permutation is there both times,
+    every field of the second visit equals the first bit for bit); cice_thermo_batch_upload forgets the concentrations
+    cice_step_therm1 kept, so the stage without aicen_init is refused behind it."""
+    import therm_itd_case as ti
+    c = lib.Context()
+    try:
+        c.thermo_set_option("sort_chunk", 256); c.thermo_set_option("sort_group", 8)
+        c.therm2_itd_times(True)
+        c.thermo_init()
+        ny, nx, nb = 29, 43, 2
+        batch, _ = _batch_inputs(ny, nx, nb, seed=33)
+        keys = ("aicen", "vicen", "vsnon", "trcrn", "eicen", "esnon", "fswsfc", "fswint", "Sswabs", "Iswabs", "mlt_onset",
+                "frz_onset") + lib.THERMO_OUT
+
+        def shape_a():
+            c.thermo_batch_alloc(nx, ny, nb)
+            b = {k: v.copy() for k, v in batch.items()}
+            c.thermo_batch_upload(b)
+            st = c.thermo_batch_step(DT, yday=150.0)
+            assert st["l_stop"] == 0 and st["n_updates"] > 0
+            c.thermo_batch_download(b)
+            assert c.evp_debug("thermo_perm").size > 0
+            return b, st["n_updates"]
+
+        r1 = shape_a()
+        nyb, nxb = 12, 14
+        small, _ = _batch_inputs(nyb, nxb, nb, seed=35)
+        c.thermo_batch_alloc(nxb, nyb, nb)
+        c.thermo_batch_upload({k: v.copy() for k, v in small.items()})
+        assert c.thermo_batch_step(DT, yday=150.0)["l_stop"] == 0
+        r2 = shape_a()
+        assert r1[1] == r2[1]
+        for k in keys:
+            assert np.array_equal(r1[0][k], r2[0][k]), k
+        # shape B again: cice_step_therm1 keeps the concentrations it found, an upload of the batch drops them
+        c.itd_init(**ti.itd_kwargs(ti.CASES["growth"]))
+        rng = np.random.default_rng(6)
+        U = lambda lo, hi: np.ascontiguousarray(rng.uniform(lo, hi, (nb, nyb, nxb)))
+        aice = np.ascontiguousarray(small["aicen"].sum(axis=1))
+        fz = dict(aice=aice, frzmlt=U(-40, 60), Tf=np.full((nb, nyb, nxb), -1.8), strocnxT=U(-0.2, 0.2), strocnyT=U(-0.2, 0.2))
+        fz["sst"] = fz["Tf"] + U(0, 0.5)
+        pc = {k: np.ascontiguousarray(rng.uniform(-1, 1, small["aicen"].shape)) for k in ("strairxn", "strairyn", "Trefn", "Qrefn")}
+        acc = {k: U(-1, 1) for k in lib.MERGE_ORDER}
+        st = {k: v.copy() for k, v in small.items()}
+        c.thermo_batch_alloc(nxb, nyb, nb)
+        assert c.step_therm1(DT, ti.YDAY, st, fz, pc, acc)["l_stop"] == 0
+        c.thermo_batch_upload(st)
+        ice = st["aicen"].sum(axis=1) > ti.PUNY
+        a = dict({k: st[k].copy() for k in ti.STATE}, vicen_init=small["vicen"].copy(), frain=U(0, 1e-5),
+                 frzmlt=fz["frzmlt"].copy(), Tf=fz["Tf"].copy(),
+                 rside=np.ascontiguousarray(np.where(ice & (fz["frzmlt"] < 0), U(0.005, 0.05), 0.0)),
+                 tmask=np.ones((nb, nyb, nxb), np.int32), aice=aice.copy(), aice0=np.maximum(1 - aice, 0),
+                 fresh=U(0, 1e-5), fsalt=U(0, 1e-7), fhocn=U(-5, 0), frazil=np.zeros((nb, nyb, nxb)),
+                 meltl=np.zeros((nb, nyb, nxb)), frz_onset=np.zeros((nb, nyb, nxb)))
+        with pytest.raises(lib.CiceError):
+            c.step_therm2_itd(DT, ti.YDAY, {k: v.copy() for k, v in a.items()}, state_resident=True)
+        a["aicen_init"] = small["aicen"].copy()
+        assert c.step_therm2_itd(DT, ti.YDAY, a, state_resident=True)["l_stop"] == 0
+        assert sum(c.therm2_itd_times()) > 0
+    finally:
+        c.close()
+
+
 def test_batch_merge_equals_merge_fluxes(ctx, orc):
     """cice_thermo_batch_merge = merge_fluxes (ice_flux.F90:613) called once per category with
     that category's list and aicen_init, on the batch's own per-category outputs: bit for bit."""
