@@ -191,28 +191,48 @@ struct StepuOut {
   double u, v, strintx, strinty, taux, tauy;
 };
 
-// One U-cell of `stepu` (ice_dyn_evp.F90:1390-1435); sx/sy are the four-term sums of :1415-1418.
+// One U-cell of `stepu` (ice_dyn_evp.F90:1390-1435) in two halves.  The head is everything that needs only the old
+// velocity and the read-only inputs; the tail is what needs the stress divergence (sx/sy: the four-term sums of
+// :1415-1418).  A kernel that has to wait for the stresses of a neighbour runs the head in front of that wait
+// (k_evp_resident).  Every value is computed by the same operations in the same order as in the reference's one loop:
+// the products Umassdtei * uold, Umassdtei * vold are terms of their own there as well (no contraction).
+struct StepuHead {
+  double taux, tauy, cca, ccb, ab2, mu, mv;
+};
+__device__ __forceinline__ void stepu_head(double uold, double vold, double Aiu, double Uocn, double Vocn,
+                                           double Waterx, double Watery, double Umassdtei, double Fm, StepuHead& h) {
+  const double du = Uocn - uold, dv = Vocn - vold;
+  const double vrel = Aiu * dragw * sqrt(du * du + dv * dv);
+  h.taux = vrel * Waterx;
+  h.tauy = vrel * Watery;
+  h.cca = Umassdtei + vrel * cosw;
+#ifdef CICE4_AMD_AUSCOM   // :1402-1408: the turning angle changes sign with the hemisphere
+  h.ccb = Fm < 0.0 ? Fm - vrel * sinw : Fm + vrel * sinw;
+#else
+  h.ccb = Fm + vrel * sinw;
+#endif
+  h.ab2 = h.cca * h.cca + h.ccb * h.ccb;
+  h.mu = Umassdtei * uold;
+  h.mv = Umassdtei * vold;
+}
+__device__ __forceinline__ void stepu_tail(const StepuHead& h, double Forcex, double Forcey, double Uarear, double sx,
+                                           double sy, StepuOut& o) {
+  o.taux = h.taux;
+  o.tauy = h.tauy;
+  o.strintx = Uarear * sx;
+  o.strinty = Uarear * sy;
+  const double cc1 = o.strintx + Forcex + h.taux + h.mu;
+  const double cc2 = o.strinty + Forcey + h.tauy + h.mv;
+  o.u = (h.cca * cc1 + h.ccb * cc2) / h.ab2;
+  o.v = (h.cca * cc2 - h.ccb * cc1) / h.ab2;
+}
 __device__ __forceinline__ void stepu_cell(double uold, double vold, double Aiu, double Uocn,
                                            double Vocn, double Waterx, double Watery, double Forcex,
                                            double Forcey, double Umassdtei, double Fm, double Uarear,
                                            double sx, double sy, StepuOut& o) {
-  const double du = Uocn - uold, dv = Vocn - vold;
-  const double vrel = Aiu * dragw * sqrt(du * du + dv * dv);
-  o.taux = vrel * Waterx;
-  o.tauy = vrel * Watery;
-  const double cca = Umassdtei + vrel * cosw;
-#ifdef CICE4_AMD_AUSCOM   // :1402-1408: the turning angle changes sign with the hemisphere
-  const double ccb = Fm < 0.0 ? Fm - vrel * sinw : Fm + vrel * sinw;
-#else
-  const double ccb = Fm + vrel * sinw;
-#endif
-  const double ab2 = cca * cca + ccb * ccb;
-  o.strintx = Uarear * sx;
-  o.strinty = Uarear * sy;
-  const double cc1 = o.strintx + Forcex + o.taux + Umassdtei * uold;
-  const double cc2 = o.strinty + Forcey + o.tauy + Umassdtei * vold;
-  o.u = (cca * cc1 + ccb * cc2) / ab2;
-  o.v = (cca * cc2 - ccb * cc1) / ab2;
+  StepuHead h;
+  stepu_head(uold, vold, Aiu, Uocn, Vocn, Waterx, Watery, Umassdtei, Fm, h);
+  stepu_tail(h, Forcex, Forcey, Uarear, sx, sy, o);
 }
 
 }  // namespace
@@ -306,6 +326,16 @@ __device__ __forceinline__ double down1z(double x) {
   int lo = __double2loint(x), hi = __double2hiint(x);
   lo = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);  // wave_shl:1
   hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// up1 with a value of its own for the lane without a source: lane 0 keeps `first`'s lane 0, every other lane gets x of the
+// lane below.  One instruction per half behind a copy of `first`, no select -- and nothing the compiler could turn into a
+// branch around the shift (a shift under an execution mask reads a masked-out source lane as missing).
+__device__ __forceinline__ double up1_first(double x, double first) {
+  int lo = __double2loint(x), hi = __double2hiint(x);
+  lo = __builtin_amdgcn_update_dpp(__double2loint(first), lo, 0x138, 0xf, 0xf, false);  // wave_shr:1
+  hi = __builtin_amdgcn_update_dpp(__double2hiint(first), hi, 0x138, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
 }
 
@@ -1580,7 +1610,9 @@ struct ResArgs {
   unsigned xg_half;      // bytes of one copy
   void* xgr;             // GRAN && FOLD: the same for the RAW velocities of the top row (the fold's own hand-off, before anything is published)
   int poll_delay, poll_sleep;   // GRAN: s_sleep(8) units (~0.2 us each) before the first poll of a subcycle / between two polls
+#ifdef CICE4_AMD_EXPERIMENTS
   int fake_ew;                  // TIMING EXPERIMENT ONLY (wrong results): the wavefronts between the first and the last row never poll
+#endif
 };
 enum { F_LO = 1, F_HI = 2, F_NEG = 4, F_SELF = 8, F_MIRROR = 16 };
 
@@ -1875,10 +1907,12 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
     };
     if (want_w) lend(q0g - 32u, lw, lw_a);
     if (want_q) lend(q0g - nxg - 32u, lq, lq_a);
+#ifdef CICE4_AMD_EXPERIMENTS
     if (r.fake_ew && w > 0 && w < W - 1) {   // (timing experiment: what the loop would cost if interior wavefronts had nothing to wait for)
       nA = nB = false;
       lw = lq = -1;
     }
+#endif
   }
   StressOut o;
   StepuOut ro{};
@@ -1923,6 +1957,10 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
 #define GRAN_COPIES 2
 #endif
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(r.xg, 0, GRAN_COPIES * r.xg_half, 0x00020000);
+    // Issue priority.  The product build knows one schedule, the four-step rotation per subcycle (below); the schedules
+    // that measured slower are compiled in -DCICE4_AMD_EXPERIMENTS builds only, so that the loop neither tests for them nor
+    // keeps their state in scalar registers.
+#ifdef CICE4_AMD_EXPERIMENTS
     const bool prio_work = r.prio_mode >= 5;     // issue priority by what a wavefront is doing: waiting 0, computing 2 (chain rows 3 in mode 5)
     const bool chain_hi = r.prio_mode == 5 && (w == 0 || w >= W - 2);
     auto prio_wait = [&]() { if (prio_work) __builtin_amdgcn_s_setprio(0); };
@@ -1932,12 +1970,19 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
         else __builtin_amdgcn_s_setprio(2);
       }
     };
+#else
+    auto prio_wait = []() {};
+    auto prio_compute = []() {};
+#endif
+    const int rot = r.prio_mode == 4 ? gen : -1;   // (uniform) the rotation's phase of this workgroup, -1: no rotation
     auto wait_row = [&](int* flag, int want) -> bool {
       long long t0 = 0;
       for (int it = 0;; ++it) {
-        if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= want) break;
+        // (every lane reads the same word: said so, the loop's exits are scalar branches and what the subcycle loop
+        //  carries in scalar registers stays there)
+        if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= want) break;
         if (it == 0) prio_wait();
-        if (__hip_atomic_load(&s_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return false;
+        if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) return false;
         if (it == 0) t0 = wall_clock64();
         else if ((it & 63) == 0 && wall_clock64() - t0 > 2 * r.spin_ticks) {   // (twice: whoever waits for memory reports first)
           if (lx == 0 && __hip_atomic_exchange(r.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
@@ -1959,21 +2004,44 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
     };
     // issue priority: the wavefronts on the chain tile -> neighbouring tile -> tile (rows 0, W-2, W-1) first
     TRACE_DECL
+#ifdef CICE4_AMD_EXPERIMENTS
     const bool chain = w == 0 || w >= W - 2;
     if (r.prio_mode == 1) {
       if (chain) __builtin_amdgcn_s_setprio(3);
       else __builtin_amdgcn_s_setprio(1);
     }
+#endif
     prio_compute();
+    // Lane 0's western and south-western velocities are handed over by v_readlane from the lane that polled them: the
+    // lender and its slot are one value per wavefront (said so with readfirstlane), so the hand-over needs neither the LDS
+    // crossbar nor a wait for it.  One scalar word each: lane | 64 if slot A, -1 if there is nothing to hand over.
+    const int lend_w = __builtin_amdgcn_readfirstlane(lw < 0 ? -1 : (lw | (lw_a ? 64 : 0)));
+    const int lend_q = __builtin_amdgcn_readfirstlane(lq < 0 ? -1 : (lq | (lq_a ? 64 : 0)));
+    const int polls = __builtin_amdgcn_readfirstlane((int)__any(nA || nB));   // does this wavefront poll at all
+    // A condition that does not change during the loop is kept by the compiler as a 64-bit lane mask in two scalar
+    // registers, of which the loop has none to spare (they were spilled and reloaded every subcycle): one scalar word,
+    // tested where it is needed, costs a compare.
+    auto word = [](int x) { asm volatile("" : "+s"(x)); return x; };
+    // the value as two scalar words out of lane `code & 63`, slot by `code & 64`, given back to every lane (a vector move)
+    auto take = [](const u32x4& ga, const u32x4& gb, int code) {
+      const bool in_a = (code & 64) != 0;
+      const int lane = code & 63;
+      return __hiloint2double(__builtin_amdgcn_readlane((int)(in_a ? ga.z : gb.z), lane),
+                              __builtin_amdgcn_readlane((int)(in_a ? ga.x : gb.x), lane));
+    };
 #pragma clang loop unroll(disable)
     for (int k = 0; k < r.nsub; ++k) {
       const bool lastk = r.last && k == r.nsub - 1;
-      if (r.prio_mode == 2) {
-        const int p = (k + gen) % 3;
-        if (p == 0) __builtin_amdgcn_s_setprio(3);
-        else if (p == 1) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      } else if (r.prio_mode == 3) {
+      if (rot >= 0) {
+        switch ((k + rot) & 3) {
+          case 0: __builtin_amdgcn_s_setprio(3); break;
+          case 1: __builtin_amdgcn_s_setprio(2); break;
+          case 2: __builtin_amdgcn_s_setprio(1); break;
+          default: __builtin_amdgcn_s_setprio(0); break;
+        }
+      }
+#ifdef CICE4_AMD_EXPERIMENTS
+      if (r.prio_mode == 3) {
         // whoever is BEHIND on its SIMD issues first: the wavefronts of a workgroup go to the SIMDs round-robin, w, w + 4, w + 8
         // share one; s_uf[] says how many subcycles each of them has finished
         int behind = 0, level = 0;
@@ -1986,15 +2054,16 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
         if (behind) __builtin_amdgcn_s_setprio(0);
         else if (level) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(3);
-      } else if (r.prio_mode == 4) {
-        const int p = (k + gen) & 3;
-        if (p == 0) __builtin_amdgcn_s_setprio(3);
-        else if (p == 1) __builtin_amdgcn_s_setprio(2);
-        else if (p == 2) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
       }
+#endif
       PHASE(7)
       TRACE(0)
+      // the metrics and the strength are this lane's own, written once before the loop: their reads are issued in front of
+      // the wait (the compiler barrier in wait_row would pin them behind it) and their latency overlaps it.  A lane
+      // without ice reads what happens to be there and never uses it.
+      double m[10];
+#pragma unroll
+      for (int c = 0; c < 10; ++c) m[c] = s_m[w][c][lx];
       // (A) velocities of the row below (LDS, from the wavefront below) and of the western neighbour
       if (w > 0) {
         if (!wait_row(&s_uf[w - 1], k)) return;
@@ -2004,24 +2073,16 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
         }
       }
       TRACE(1)
-      double uw = up1(un), vw = up1(vn), usw = up1(us), vsw = up1(vs);
-      if (lx == 0) {
-        uw = uwh;
-        vw = vwh;
-        usw = uswh;
-        vsw = vswh;
-      }
+      // (lane 0 of the shifted rows is lane 0's western column: the shift leaves it in place)
+      const double uw = up1_first(un, uwh), vw = up1_first(vn, vwh), usw = up1_first(us, uswh), vsw = up1_first(vs, vswh);
       // (B) stress (ice_dyn_evp.F90:1065-1289)
 #pragma unroll
       for (int c = 0; c < 8; ++c) o.str[c] = c0;
       if (tact) {
-        const double Dxt = s_m[w][0][lx], Dyt = s_m[w][1][lx], Dxhy = s_m[w][2][lx], Dyhx = s_m[w][3][lx],
-                     Cxp = s_m[w][5][lx], Cyp = s_m[w][6][lx], Cxm = s_m[w][7][lx], Cym = s_m[w][8][lx],
-                     Tiny = s_m[w][9][lx];
-        stress_cell<true, DAMP>(a.sc, un, uw, usw, us, vn, vw, vsw, vs, Dxt, Dyt, Dxhy, Dyhx, Cxp, Cyp, Cxm, Cym,
-                                lastk ? a.tarear[q] : c0, Tiny, s_m[w][4][lx], s, o, lastk);
+        stress_cell<true, DAMP>(a.sc, un, uw, usw, us, vn, vw, vsw, vs, m[0], m[1], m[2], m[3], m[5], m[6], m[7], m[8],
+                                lastk ? a.tarear[q] : c0, m[9], m[4], s, o, lastk);
       }
-      const double e1 = down1(o.str[1]), e3 = down1(o.str[3]), e6 = down1(o.str[6]), e7 = down1(o.str[7]);
+      const double e1 = down1z(o.str[1]), e3 = down1z(o.str[3]), e6 = down1z(o.str[6]), e7 = down1z(o.str[7]);
       if (w > 0) {
         s_edge[w][0][lx] = o.str[2];
         s_edge[w][1][lx] = e3;
@@ -2033,17 +2094,28 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
       PHASE(0)       // 0: row below seen + stress
       // (C) momentum (:1390-1435): str of the eastern neighbour by wave shift, of the row above through LDS
       if (w < W - 1) {
+        // the half of the momentum equation that needs no stress runs while the wavefront above finishes its own: the
+        // read-only inputs are read, and the head computed, in front of the wait
+        StepuHead hd{};
+        double forcex = c0, forcey = c0, uarear = c0;
+        if (uact) {
+          const double uocn = s_x[w][1][lx], vocn = s_x[w][2][lx], fm = s_x[w][6][lx];
+          double wx, wy;
+          water_of(uocn, vocn, fm, wx, wy);
+          stepu_head(un, vn, s_x[w][0][lx], uocn, vocn, wx, wy, s_x[w][5][lx], fm, hd);
+          forcex = s_x[w][3][lx];
+          forcey = s_x[w][4][lx];
+          uarear = s_x[w][7][lx];
+        }
+        // (the head's results exist before the wait begins: nothing of it is left to be computed behind it)
+        asm volatile("" : "+v"(hd.taux), "+v"(hd.tauy), "+v"(hd.cca), "+v"(hd.ccb), "+v"(hd.ab2), "+v"(hd.mu), "+v"(hd.mv));
         if (!wait_row(&s_sf[w + 1], k + 1)) return;
         TRACE(3)
         PHASE(1)     // 1: str row of the wavefront above seen
         if (uact) {
           const double sx = o.str[0] + e1 + s_edge[w + 1][0][lx] + s_edge[w + 1][1][lx];   // :1415-1416 order
           const double sy = o.str[4] + s_edge[w + 1][2][lx] + e6 + s_edge[w + 1][3][lx];   // :1417-1418 order
-          const double uocn = s_x[w][1][lx], vocn = s_x[w][2][lx];
-          double wx, wy;
-          water_of(uocn, vocn, s_x[w][6][lx], wx, wy);
-          stepu_cell(un, vn, s_x[w][0][lx], uocn, vocn, wx, wy,
-                     s_x[w][3][lx], s_x[w][4][lx], s_x[w][5][lx], s_x[w][6][lx], s_x[w][7][lx], sx, sy, ro);
+          stepu_tail(hd, forcex, forcey, uarear, sx, sy, ro);
           un = ro.u;
           vn = ro.v;
         }
@@ -2146,12 +2218,14 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
       PHASE(2)       // 2: momentum, granule stores issued, row posted
       // (E) this wavefront polls the cells its own lanes need
       bool pa = nA, pb = nB;
-      if (__any(pa || pb)) {
+      if (polls) {
         prio_wait();
         const long long t0 = wall_clock64();
         int it = 0;
-        for (int d = 0; d < r.poll_delay; ++d) __builtin_amdgcn_s_sleep(8);
-        u32x4 a0 = {0u, 0u, 0u, 0u}, a1 = a0, b0 = a0, b1 = a0;
+        for (int d = word(r.poll_delay); d > 0; --d) __builtin_amdgcn_s_sleep(8);
+        // (a lane that polls nothing keeps whatever these registers hold and never looks at it: nothing to clear)
+        u32x4 a0, a1, b0, b1;
+        asm volatile("" : "=v"(a0), "=v"(a1), "=v"(b0), "=v"(b1));
         while (true) {
           if (pa) { a0 = ld_gran(rs, offA, par); a1 = ld_gran(rs, offA + 16u, par); }
           if (pb) { b0 = ld_gran(rs, offB, par); b1 = ld_gran(rs, offB + 16u, par); }
@@ -2190,14 +2264,11 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
         const double au = gran_val(a0), av = gran_val(a1), bu = gran_val(b0), bv = gran_val(b1);
         if (need_f) { un = au; vn = av; }
         if (need_s) { us = bu; vs = bv; }
-        if (lw >= 0) {
-          const double xu_ = __shfl(lw_a ? au : bu, lw), xv_ = __shfl(lw_a ? av : bv, lw);
-          if (lx == 0) { uwh = xu_; vwh = xv_; }
-        }
-        if (lq >= 0) {
-          const double xu_ = __shfl(lq_a ? au : bu, lq), xv_ = __shfl(lq_a ? av : bv, lq);
-          if (lx == 0) { uswh = xu_; vswh = xv_; }
-        }
+        // lane 0's western / south-western values, straight from the granules of the lane that polled them (words x and z:
+        // the two halves of the value)
+        const int cw = word(lend_w), cq = word(lend_q);
+        if (cw >= 0) { uwh = take(a0, b0, cw); vwh = take(a1, b1, cw); }
+        if (cq >= 0) { uswh = take(a0, b0, cq); vswh = take(a1, b1, cq); }
         prio_compute();
       }
       TRACE(5)
@@ -2224,13 +2295,8 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
       us = s_uv[w - 1][0][lx];
       vs = s_uv[w - 1][1][lx];
     }
-    double uw = up1(un), vw = up1(vn), usw = up1(us), vsw = up1(vs);
-    if (lx == 0) {
-      uw = uwh;
-      vw = vwh;
-      usw = uswh;
-      vsw = vswh;
-    }
+    // (lane 0 of the shifted rows is lane 0's western column: the shift leaves it in place; lane 63 owns no U-cell)
+    const double uw = up1_first(un, uwh), vw = up1_first(vn, vwh), usw = up1_first(us, uswh), vsw = up1_first(vs, vswh);
     // (B) stress (ice_dyn_evp.F90:1065-1289)
 #pragma unroll
     for (int c = 0; c < 8; ++c) o.str[c] = c0;
@@ -2242,7 +2308,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
                               lastk ? a.tarear[q] : c0, Tiny, s_m[w][4][lx], s, o, lastk);
     }
     // (C) momentum (:1390-1435): str of the eastern neighbour by wave shift, of the row above through LDS
-    const double e1 = down1(o.str[1]), e3 = down1(o.str[3]), e6 = down1(o.str[6]), e7 = down1(o.str[7]);
+    const double e1 = down1z(o.str[1]), e3 = down1z(o.str[3]), e6 = down1z(o.str[6]), e7 = down1z(o.str[7]);
     if (w > 0) {
       s_edge[w][0][lx] = o.str[2];
       s_edge[w][1][lx] = e3;
@@ -2250,17 +2316,25 @@ __global__ __launch_bounds__(64 * W, (W == 4 && !PEER ? 3 : (64 * W + 255) / 256
       s_edge[w][3][lx] = e7;
     }
     PHASE(0)         // 0: stress
+    // the half of the momentum equation that needs no stress, in front of the barrier
+    StepuHead hd{};
+    double forcex = c0, forcey = c0, uarear = c0;
+    if (uact) {
+      const double uocn = s_x[w][1][lx], vocn = s_x[w][2][lx], fm = s_x[w][6][lx];
+      // waterx, watery are evp_prep2's own expressions of uocn, vocn (:915-916): recomputed, same bits
+      double wx, wy;
+      water_of(uocn, vocn, fm, wx, wy);
+      stepu_head(un, vn, s_x[w][0][lx], uocn, vocn, wx, wy, s_x[w][5][lx], fm, hd);
+      forcex = s_x[w][3][lx];
+      forcey = s_x[w][4][lx];
+      uarear = s_x[w][7][lx];
+    }
     __syncthreads();
     PHASE(1)         // 1: barrier (C)
     if (uact) {
       const double sx = o.str[0] + e1 + s_edge[w + 1][0][lx] + s_edge[w + 1][1][lx];   // :1415-1416 order
       const double sy = o.str[4] + s_edge[w + 1][2][lx] + e6 + s_edge[w + 1][3][lx];   // :1417-1418 order
-      const double uocn = s_x[w][1][lx], vocn = s_x[w][2][lx];
-      // waterx, watery are evp_prep2's own expressions of uocn, vocn (:915-916): recomputed, same bits
-      double wx, wy;
-      water_of(uocn, vocn, s_x[w][6][lx], wx, wy);
-      stepu_cell(un, vn, s_x[w][0][lx], uocn, vocn, wx, wy,
-                 s_x[w][3][lx], s_x[w][4][lx], s_x[w][5][lx], s_x[w][6][lx], s_x[w][7][lx], sx, sy, ro);
+      stepu_tail(hd, forcex, forcey, uarear, sx, sy, ro);
       un = ro.u;
       vn = ro.v;
     }
@@ -3045,6 +3119,9 @@ void Evp::set_option(const char* key, int value) {
     CICE_REQUIRE(value >= 0, "resident_spin_us must be >= 0");
     res_spin_us = value;
   } else if (!std::strcmp(key, "resident_prio")) {    // issue priority among the workgroups of a CU (dense shape): 0, 1, 2
+    // granule loop: 0 none, 2 or 4 the four-step rotation per subcycle (the default).  1 (chain rows first), 3 (whoever is
+    // behind on its SIMD first), 5 and 6 (by what a wavefront is doing) measured slower and are compiled in
+    // -DCICE4_AMD_EXPERIMENTS builds only: the product build accepts them and runs the default in their place.
     CICE_REQUIRE(value >= 0 && value <= 6, "resident_prio must be 0 .. 6");
     res_prio = value;
   } else if (!std::strcmp(key, "resident_dense")) {   // three 4-wavefront workgroups per CU where that fills the chip
@@ -5789,8 +5866,10 @@ bool Evp::run_resident(int ksub0, int nsub) {
     static const int ps = [] { const char* e = std::getenv("CICE4_AMD_RESIDENT_POLL_SLEEP"); return e ? std::atoi(e) : 0; }();
     r.poll_delay = pd;
     r.poll_sleep = ps;
+#ifdef CICE4_AMD_EXPERIMENTS   // (a timing experiment that gives wrong results: not in the product build, nor its environment variable)
     static const int fk = [] { const char* e = std::getenv("CICE4_AMD_RESIDENT_FAKE_EW"); return e ? std::atoi(e) : 0; }();
     r.fake_ew = fk;
+#endif
   } else {
     for (int k = 0; k < 2; ++k)   // cells nobody publishes keep their value: both exchange copies start as (u, v)
       CICE_HIP(hipMemcpyAsync(res_xu[k].p, uv[cur].p, 2 * n * 8, hipMemcpyDeviceToDevice, stream));
@@ -5809,7 +5888,13 @@ bool Evp::run_resident(int ksub0, int nsub) {
     }
   }
   // (the granule loop: a four-step rotation, 196.6 k subcycles/s at gx1 against 194.5 k with the three-step one and 169 k without)
+  // (the schedules that measured slower -- 1, 3, 5, 6 -- exist in -DCICE4_AMD_EXPERIMENTS builds only: the product build runs the
+  //  rotation in their place)
+#ifdef CICE4_AMD_EXPERIMENTS
   r.prio_mode = gran ? (res_prio == 2 ? 4 : res_prio) : (dense ? std::min(res_prio, 2) : 0);
+#else
+  r.prio_mode = gran ? (res_prio == 0 ? 0 : 4) : (dense ? std::min(res_prio, 2) : 0);
+#endif
   {
     static const bool top = [] { const char* e = std::getenv("CICE4_AMD_RESIDENT_PRIO_TOP"); return !(e && e[0] == '0'); }();
     r.prio_top = dense && top ? 1 : 0;
