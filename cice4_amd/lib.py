@@ -538,17 +538,37 @@ class Context:
             assert field.dtype == np.int32
             self._ck(self.lib.cice_halo_update_blocked_i4(self.h, p, nz, loc, kind, C.c_int32(int(fill))))
 
-    def halo_update_resident(self, field):
+    def halo_update_strided(self, section, loc=1, kind=1, fill=0):
+        """The same for a SECTION of a 4-d module array (cice_halo_update_strided_r8): a float64 view
+        (nblocks, nz2, nz1, ny, nx) whose horizontal planes are whole and whose levels and blocks are strided, e.g.
+        trcrn[:, :, 0:ntrcr] of an array (nblocks, ncat, max_ntrcr, ny, nx).  Updated in place; nothing outside the
+        section is touched."""
+        assert section.dtype == np.float64 and section.ndim == 5
+        nb, nz2, nz1, ny, nx = section.shape
+        assert (nb, ny, nx) == (self.nblocks, self.ny, self.nx)
+        sb, s2, s1, sy, sx = (s // 8 for s in section.strides)
+        assert (sy, sx) == (nx, 1) and all(s % 8 == 0 for s in section.strides), "the horizontal planes must be whole"
+        self._ck(self.lib.cice_halo_update_strided_r8(self.h, C.c_void_p(section.ctypes.data), nz1, C.c_longlong(s1), nz2,
+                                                      C.c_longlong(s2), C.c_longlong(sb), loc, kind, C.c_double(fill)))
+
+    def halo_update_resident(self, field, loc=1, kind=1, fill=0):
         """The same on a field kept in device memory: upload once, update through cice_halo_update_dev_r8/_i4
-        (all levels in one message per neighbour, no staging, no allocation per call), download."""
+        (all levels in one message per neighbour, no staging, no allocation per call), download.  With a location,
+        kind or fill value other than the defaults: cice_halo_update_dev_ex_r8 (float64 only)."""
         n = self.nblocks * self.ny * self.nx
         nlev = field.size // n
+        plain = (loc, kind, fill) == (1, 1, 0)
+        if not plain and field.dtype != np.float64:
+            raise CiceError("halo_update_resident: location / kind / fill on a resident field are float64 only")
         dev = C.c_void_p()
         self._ck(self.lib.cice_device_alloc(self.h, C.c_size_t(field.nbytes), C.byref(dev)))
         try:
             self._ck(self.lib.cice_device_copy(self.h, dev, _p(field), C.c_size_t(field.nbytes), 1))
-            fn = self.lib.cice_halo_update_dev_r8 if field.dtype == np.float64 else self.lib.cice_halo_update_dev_i4
-            self._ck(fn(self.h, dev, nlev))
+            if plain:
+                fn = self.lib.cice_halo_update_dev_r8 if field.dtype == np.float64 else self.lib.cice_halo_update_dev_i4
+                self._ck(fn(self.h, dev, nlev))
+            else:
+                self._ck(self.lib.cice_halo_update_dev_ex_r8(self.h, dev, nlev, loc, kind, C.c_double(fill)))
             self._ck(self.lib.cice_device_copy(self.h, _p(field), dev, C.c_size_t(field.nbytes), 0))
         finally:
             self._ck(self.lib.cice_device_free(self.h, dev))

@@ -525,6 +525,53 @@ contains
       endif
    end subroutine ref_halo_nd
 
+   ! the same with fillValue (the value of ghost cells facing eliminated blocks and of the gaps they leave in the
+   ! tripole buffer), handed over as a double and converted to the field's own kind
+   subroutine ref_halo_nd_fill(buf, typ, nz, nt, loc, kind, fill) bind(C, name='ref_halo_nd_fill')
+      use ice_kinds_mod, only: real_kind, int_kind
+      use ice_blocks, only: nx_block, ny_block
+      use ice_boundary
+      use ice_domain, only: halo_info
+      type(c_ptr), value :: buf
+      integer(c_int), value :: typ, nz, nt, loc, kind
+      real(c_double), value :: fill
+      real(c_double), pointer :: d2(:,:,:), d3(:,:,:,:), d4(:,:,:,:,:)
+      real(c_float), pointer :: f2(:,:,:), f3(:,:,:,:), f4(:,:,:,:,:)
+      integer(c_int), pointer :: i2(:,:,:), i3(:,:,:,:), i4(:,:,:,:,:)
+      real(real_kind) :: fill4
+      integer(int_kind) :: filli
+      fill4 = real(fill, real_kind)
+      filli = nint(fill)
+      if (nz == 0) then
+         select case (typ)
+         case (0); call c_f_pointer(buf, d2, [nx_block,ny_block,max_blocks])
+                   call ice_HaloUpdate(d2, halo_info, loc, kind, fillValue=fill)
+         case (1); call c_f_pointer(buf, f2, [nx_block,ny_block,max_blocks])
+                   call ice_HaloUpdate(f2, halo_info, loc, kind, fillValue=fill4)
+         case (2); call c_f_pointer(buf, i2, [nx_block,ny_block,max_blocks])
+                   call ice_HaloUpdate(i2, halo_info, loc, kind, fillValue=filli)
+         end select
+      else if (nt == 0) then
+         select case (typ)
+         case (0); call c_f_pointer(buf, d3, [nx_block,ny_block,nz,max_blocks])
+                   call ice_HaloUpdate(d3, halo_info, loc, kind, fillValue=fill)
+         case (1); call c_f_pointer(buf, f3, [nx_block,ny_block,nz,max_blocks])
+                   call ice_HaloUpdate(f3, halo_info, loc, kind, fillValue=fill4)
+         case (2); call c_f_pointer(buf, i3, [nx_block,ny_block,nz,max_blocks])
+                   call ice_HaloUpdate(i3, halo_info, loc, kind, fillValue=filli)
+         end select
+      else
+         select case (typ)
+         case (0); call c_f_pointer(buf, d4, [nx_block,ny_block,nz,nt,max_blocks])
+                   call ice_HaloUpdate(d4, halo_info, loc, kind, fillValue=fill)
+         case (1); call c_f_pointer(buf, f4, [nx_block,ny_block,nz,nt,max_blocks])
+                   call ice_HaloUpdate(f4, halo_info, loc, kind, fillValue=fill4)
+         case (2); call c_f_pointer(buf, i4, [nx_block,ny_block,nz,nt,max_blocks])
+                   call ice_HaloUpdate(i4, halo_info, loc, kind, fillValue=filli)
+         end select
+      endif
+   end subroutine ref_halo_nd_fill
+
    subroutine ref_halo_extrapolate(a) bind(C, name='ref_halo_extrapolate')
       use ice_blocks, only: nx_block, ny_block
       use ice_boundary

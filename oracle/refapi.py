@@ -309,15 +309,20 @@ class Ref:
         """transport_upwind(dt) (ice_transport_driver.F90:672) on the module state."""
         self.lib.ref_transport_upwind(C.c_double(dt))
 
-    def halo_nd(self, a, loc=1, kind=1):
+    def halo_nd(self, a, loc=1, kind=1, fill=None):
         """Generic ice_HaloUpdate on a C-ordered array (nblk[,nt][,nz],ny,nx) of float64,
-        float32 or int32 -- the 2-d/3-d/4-d x R8/R4/I4 specifics."""
+        float32 or int32 -- the 2-d/3-d/4-d x R8/R4/I4 specifics.  fill: the update's fillValue
+        (ref_halo_nd_fill); None leaves the optional argument out (ref_halo_nd)."""
         typ = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}[a.dtype]
         assert a.shape[0] == self.max_blocks and a.shape[-2:] == (self.ny_block, self.nx_block)
         nz = a.shape[-3] if a.ndim >= 4 else 0
         nt = a.shape[-4] if a.ndim == 5 else 0
-        self.lib.ref_halo_nd(_p(a), C.c_int(typ), C.c_int(nz), C.c_int(nt), C.c_int(loc),
-                             C.c_int(kind))
+        if fill is None:
+            self.lib.ref_halo_nd(_p(a), C.c_int(typ), C.c_int(nz), C.c_int(nt), C.c_int(loc),
+                                 C.c_int(kind))
+        else:
+            self.lib.ref_halo_nd_fill(_p(a), C.c_int(typ), C.c_int(nz), C.c_int(nt), C.c_int(loc),
+                                      C.c_int(kind), C.c_double(fill))
 
     def halo_extrapolate(self, a):
         self.lib.ref_halo_extrapolate(_p(a))

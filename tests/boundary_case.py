@@ -1,7 +1,7 @@
 """One boundary-module comparison in its own process (the compiled reference allows ONE
 init_domain per process and library).  Started by tests/test_boundary.py:
 
-    python tests/boundary_case.py lists <cfg> <ew> <ns> [gx3 grid dir]
+    python tests/boundary_case.py lists <cfg> <ew> <ns> [gx3 | gx3-landtop]
                                                           CPU: the product's halo lists applied in
                                                           numpy == the reference's ice_HaloUpdate
     python tests/boundary_case.py gpu   <cfg> <ew> <ns>   MI355X: the reference's callers linked with
@@ -40,8 +40,12 @@ def main():
         with open(os.path.join(d, "global_gx3.grid"), "wb") as f:
             for k in ("ULAT", "ULON", "HTN", "HTE", "HUS", "HUW", "ANGLE"):
                 f.write(z[k].astype(">f8").tobytes())
+        kmt = z["kmt"].copy()
+        if sys.argv[5] == "gx3-landtop":    # block (4, 12) of the 10 x 12 blocks of gx3e made land: the reference drops a
+            assert kmt.shape == (116, 100)  # block of the TOP row too, which leaves a gap in the tripole buffer
+            kmt[110:116, 30:40] = 0
         with open(os.path.join(d, "global_gx3.kmt"), "wb") as f:
-            f.write(z["kmt"].astype(">i4").tobytes())
+            f.write(kmt.astype(">i4").tobytes())
         gridkw = dict(grid="displaced_pole", grid_file=os.path.join(d, "global_gx3.grid"),
                       kmt_file=os.path.join(d, "global_gx3.kmt"))
     from __graft_entry__ import REF_CONFIGS
@@ -74,26 +78,39 @@ def main():
             assert np.array_equal(plain["hsrc"], dom["hsrc"]) and np.array_equal(plain["hdst"], dom["hdst"])
         locs = (1, 2, 3, 4) if ns.startswith("tripole") else (1,)
         kinds = (1, 2, 3) if ns.startswith("tripole") else (1,)
+        # fillValue: left out (0, ref_halo_nd) everywhere; where blocks are eliminated also a non-zero one handed to the
+        # reference's update (ref_halo_nd_fill) -- ghost cells facing an eliminated block take it, and under a fold the
+        # gap an eliminated top-row block leaves in the buffer comes out as sign * fillValue
+        fills = {np.float64: (None, -3.5), np.float32: (None, -3.5), np.int32: (None, 7)} if cfg == "gx3e" else {}
+        if sys.argv[5:] == ["gx3-landtop"]:
+            assert owner[113] == -1 and ref.nblocks == nbx * nby - 5
+            gap = np.ones(int(c.domain_list("fold_bidx").max()) + 1, bool); gap[c.domain_list("fold_bidx")] = False
+            assert gap.any() and all(gap[c.domain_list("fold_src", l)].any() for l in locs)   # a top-row block is gone
         for dtype in (np.float64, np.float32, np.int32):
             for loc in locs:
                 for kind in kinds:
-                    a = rand(rng, (nb, ny, nx), dtype)
-                    want = a.copy(); ref.halo_nd(want, loc, kind)
-                    got = a.copy()
-                    c.apply_halo_lists(got[:dom["nblocks"]], loc, kind, fill=0)
-                    assert np.array_equal(got, want), (dtype, ew, ns, loc, kind, np.argwhere(got != want)[:8])
-                    assert not np.array_equal(want, a)
-                    nchk += 1
-                    # the C-ABI entry the boundary module calls with a HOST array (cice_halo_update_blocked_*): on a
-                    # one-rank domain the lists are applied on the host inside the caller's array (no device), in the
-                    # reference's layout (block outermost, levels inside) -- 1 and 3 levels
-                    for shape in ((nb, ny, nx), (nb, 3, ny, nx)):
-                        a = rand(rng, shape, dtype)
-                        want = a.copy(); ref.halo_nd(want, loc, kind)
+                    for fill in fills.get(dtype, (None,)):
+                        a = rand(rng, (nb, ny, nx), dtype)
+                        want = a.copy(); ref.halo_nd(want, loc, kind, fill)
                         got = a.copy()
-                        c.halo_update_blocked(got[:dom["nblocks"]].reshape(dom["nblocks"], -1, ny, nx), loc, kind, fill=0)
-                        assert np.array_equal(got, want), ("blocked", dtype, shape, ew, ns, loc, kind)
+                        c.apply_halo_lists(got[:dom["nblocks"]], loc, kind, fill=fill or 0)
+                        assert np.array_equal(got, want), (dtype, ew, ns, loc, kind, fill, np.argwhere(got != want)[:8])
+                        assert not np.array_equal(want, a)
+                        if fill is not None:    # the fill value shows: the same field updated with fill 0 differs
+                            zero = a.copy(); ref.halo_nd(zero, loc, kind)
+                            assert not np.array_equal(zero, want)
                         nchk += 1
+                        # the C-ABI entry the boundary module calls with a HOST array (cice_halo_update_blocked_*): on a
+                        # one-rank domain the lists are applied on the host inside the caller's array (no device), in the
+                        # reference's layout (block outermost, levels inside) -- 1 and 3 levels
+                        for shape in ((nb, ny, nx), (nb, 3, ny, nx)):
+                            a = rand(rng, shape, dtype)
+                            want = a.copy(); ref.halo_nd(want, loc, kind, fill)
+                            got = a.copy()
+                            c.halo_update_blocked(got[:dom["nblocks"]].reshape(dom["nblocks"], -1, ny, nx), loc, kind,
+                                                  fill=fill or 0)
+                            assert np.array_equal(got, want), ("blocked", dtype, shape, ew, ns, loc, kind, fill)
+                            nchk += 1
         print("BOUNDARY-OK", nchk)
         return
 
