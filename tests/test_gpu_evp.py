@@ -245,8 +245,12 @@ def test_errors_are_reported_not_fatal(ctx):
         c2.domain_create(10, 10, 20, 20, ew=7)
 
 
-@pytest.mark.parametrize("cfg,kind", [("gx3b4", "dropin"), ("gx3b4", "dropinmpi"), ("padx", "dropin")])
-def test_fortran_dropin_module_inside_reference_callers(orc, cfg, kind):
+@pytest.mark.parametrize("cfg,kind,strength", [
+    pytest.param("gx3b4", "dropin", (1, 0, 0, 4.0), id="gx3b4-dropin"),
+    pytest.param("gx3b4", "dropinmpi", (1, 0, 0, 4.0), id="gx3b4-dropinmpi"),
+    pytest.param("padx", "dropin", (1, 0, 0, 4.0), id="padx-dropin"),
+    pytest.param("gx3b4", "dropin", (1, 0, 1, 3.0), id="gx3b4-dropin-redist1-mu3")])
+def test_fortran_dropin_module_inside_reference_callers(orc, cfg, kind, strength):
     """The drop-in proof: the reference's own compiled modules (ice_state, ice_flux, ice_grid,
     ice_domain, ... and the capture wrapper that calls `evp(dt)`) linked with OUR
     cice4_amd/fortran/ice_dyn_evp.F90 instead of the reference's.  `call evp(dt)` then goes
@@ -257,7 +261,9 @@ def test_fortran_dropin_module_inside_reference_callers(orc, cfg, kind):
     job): our boundary module then also broadcasts the RCCL id over MPI_COMM_ICE and creates the RCCL
     communicator, as every task of an MPI build does.
     cfg 'padx': 3x3 blocks with padded last blocks in arrays dimensioned max_blocks = 12 > 9, as on a
-    task of an MPI run that owns fewer blocks than the largest share."""
+    task of an MPI run that owns fewer blocks than the largest share.
+    strength (kstrength, krdg_partic, krdg_redist, mu_rdg), exp-free either way: the last case carries krdg_redist and a
+    mu_rdg other than the default from ice_mechred through the shim into the library's configuration."""
     import tempfile
     from __graft_entry__ import REF_CONFIGS
     from oracle import refapi
@@ -284,7 +290,7 @@ def test_fortran_dropin_module_inside_reference_callers(orc, cfg, kind):
               "uarear", "tinyarea", "fcor", "HTN", "HTE"):
         ref.set(k, full(grid[k]))
     ref.set("tmask", full(grid["tmask"].astype(float))); ref.set("umask", full(grid["umask"].astype(float)))
-    ref.set_strength_parameters(1, 0, 0, 4.0)      # exp-free strength: bit-for-bit comparison
+    ref.set_strength_parameters(*strength)         # exp-free strength: bit-for-bit comparison
     ref.evp_gpu_setup()
     for k in ("aice", "vice", "vsno", "aice0", "strairxT", "strairyT", "uocn", "vocn", "ss_tltx", "ss_tlty",
               "uvel", "vvel", "fm", "strtltx", "strtlty", "strocnx", "strocny", "strintx",
@@ -293,7 +299,7 @@ def test_fortran_dropin_module_inside_reference_callers(orc, cfg, kind):
     ref.set("iceumask", full(s["iceumask"].astype(float)))
     ref.set("aicen", full(s["aicen"].reshape(-1, ny, nx))); ref.set("vicen", full(s["vicen"].reshape(-1, ny, nx)))
     ref.evp(DT)
-    orc.set_evp_parameters(DT, NDTE, False); orc.set_strength_parameters(1, 0, 0, 4.0)
+    orc.set_evp_parameters(DT, NDTE, False); orc.set_strength_parameters(*strength)
     so = {k: v.copy() for k, v in s.items()}
     orc.evp(orc.make_domain(dom, grid), so)
     orc.set_strength_parameters()
