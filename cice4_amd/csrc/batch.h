@@ -6,8 +6,10 @@
 #include <vector>
 
 #include "atmo.h"
+#include "cleanup.h"
 #include "common.h"
 #include "domain.h"
+#include "halo.h"
 #include "itd.h"
 #include "therm.h"
 
@@ -20,6 +22,8 @@ enum { A_AICEN = 0, A_TRCRN = 1, A_VICEN = A_TRCRN + NTRCR, A_VSNON, A_EICEN, A_
        A_FSWINT, A_FSWTHRU, A_SSW, A_ISW = A_SSW + NSLYR, A_OUT = A_ISW + NILYR, A_MLT = A_OUT + 15,
        A_FRZ, A_END };
 // the (nx, ny[, nblocks]) fields of the thickness-distribution stage in the order they are staged
+// device times of cice_therm2_cleanup_times: head, the eight passes, zap, bound_state, aggregate
+enum { CLEAN_TIMES = 12 };
 enum { I2_AICE = 0, I2_AICE0, I2_FRAIN, I2_FRZMLT, I2_TF, I2_RSIDE, I2_FRESH, I2_FSALT, I2_FHOCN, I2_FRAZIL, I2_MELTL,
        I2_FRZ_ONSET };
 
@@ -90,8 +94,12 @@ class ColumnBatch {
                    long long* n_updates, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* nstop, int32_t* bstop);
   void step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, double dt, double yday, const cice_therm2_fields* f,
                        int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
+  // halo: the context's ghost-cell update (bound = 1) or nullptr
+  void step_therm2_cleanup(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, Halo* halo, int32_t* l_stop,
+                           int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
   void set_option(const char* key, int value);      // before or after alloc; kept across re-allocations
   void itd_times(bool enable, float ms[4]);         // likewise
+  void cleanup_times(bool enable, float ms[CLEAN_TIMES]);
   // "thermo_niter", one byte per (cell, category); "thermo_perm", the permutation of the last sorted step as int32 -- either
   // packed in 8-byte words.  Returns their number, -1 for another name.
   long long debug_read(const char* what, long long* out, long long cap) const;
@@ -133,6 +141,14 @@ class ColumnBatch {
   hipEvent_t itd_ev_[5] = {};
   bool itd_timed_ = false;
   float itd_ms_[4] = {0, 0, 0, 0};
+  // cleanup stage: the state is what step_therm2_itd left (all ntrcr tracer planes); its 2-d fields, tmask, block words
+  bool therm2_state_ = false;
+  DevBuf<double> clean_b_, clean_t_;
+  DevBuf<int32_t> clean_bi_;
+  DevBuf<unsigned long long> clean_w_;
+  hipEvent_t clean_ev_[CLEAN_TIMES + 1] = {};
+  bool clean_timed_ = false;
+  float clean_ms_[CLEAN_TIMES] = {};
 };
 
 }  // namespace cice

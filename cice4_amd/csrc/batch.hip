@@ -41,6 +41,8 @@ unsigned long long itd_shift_key(const unsigned long long* r, int N) {
 ColumnBatch::~ColumnBatch() {
   for (hipEvent_t e : itd_ev_)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : clean_ev_)
+    if (e) (void)hipEventDestroy(e);
 }
 
 // Every field of cice_thermo_fields, once, in the order the fields travel: what alloc sizes, upload and download move
@@ -72,6 +74,7 @@ void ColumnBatch::alloc(hipStream_t stream, CopyFan& fan, int nx, int ny, int nb
   stream_ = stream; fan_ = &fan;
   nx_ = nx; ny_ = ny; nb_ = nb;
   kept_aicen_init_ = false;
+  therm2_state_ = false;
   const size_t np = (size_t)nx * ny, n2 = np * nb, nc = n2 * NCAT;
   std::vector<int32_t> hb;
   if (dom && same_layout(*dom)) {
@@ -128,6 +131,7 @@ void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields
 
 void ColumnBatch::upload(const ThermoParams* tp, const cice_thermo_fields* h) {
   kept_aicen_init_ = false;
+  therm2_state_ = false;
   upload_fields(tp, h, true, true);
   CICE_HIP(hipStreamSynchronize(stream_));
 }
@@ -189,6 +193,7 @@ void ColumnBatch::set_option(const char* key, int value) {
 void ColumnBatch::step(const ThermoParams* tp, double dt, double yday, long long* n_updates, int32_t* l_stop, int32_t* istop,
                        int32_t* jstop, int32_t* nstop, int32_t* bstop, float* elapsed_ms) {
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
+  therm2_state_ = false;
   unsigned long long h[THERMO_STATUS_WORDS];
   hipEvent_t ev[2] = {nullptr, nullptr};
   launch_step(*tp, dt, yday, h, elapsed_ms, ev);
@@ -272,6 +277,7 @@ void ColumnBatch::step_therm1(const ThermoParams* tp, double chio, double dt, do
   CICE_REQUIRE(st && fz && mg && l_stop && istop && jstop, "NULL argument");
   CICE_REQUIRE(fz->aice && fz->frzmlt && fz->sst && fz->Tf && fz->strocnxT && fz->strocnyT, "NULL frzmlt input");
   hipStream_t s = stream_;
+  therm2_state_ = false;
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
   // every upload first, spread over the side streams (about 150 separate host arrays), then the kernels
   fan_->fork(s);
@@ -361,6 +367,7 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
   CICE_REQUIRE(f->aicen_init || kept_aicen_init_,
                "cice_step_therm2_itd: aicen_init = NULL needs a cice_step_therm1 call on this batch in front");
   hipStream_t s = stream_;
+  therm2_state_ = false;
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
   if (itd_b_.n < 2 * nc + 12 * n2) itd_b_.alloc(2 * nc + 12 * n2);
   if (itd_bi_.n < n2 + (size_t)nb_) itd_bi_.alloc(n2 + (size_t)nb_);
@@ -454,6 +461,128 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
     if (out2[k]) CICE_HIP(hipMemcpyAsync(out2[k], d2 + (size_t)k * n2, n2 * 8, hipMemcpyDeviceToHost, cs()));
   fan_->join();
   CICE_HIP(hipStreamSynchronize(s));
+  therm2_state_ = !*l_stop;            // the state with all its tracer planes is on the device (step_therm2_cleanup)
+}
+
+// The second half of step_therm2 on the batch (ice_step_mod.F90:445-511): see include/cice4_amd.h and cleanup.h
+void ColumnBatch::step_therm2_cleanup(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, Halo* halo,
+                                      int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage) {
+  CICE_REQUIRE(ip, "cice_itd_init has not been called");
+  CICE_REQUIRE(dt > 0.0, "dt");
+  CICE_REQUIRE(f->aicen && f->trcrn && f->vicen && f->vsnon && f->eicen && f->esnon && f->tmask && f->aice && f->aice0 &&
+                   f->vice && f->vsno && f->eice && f->esno && f->trcr && f->fresh && f->fsalt && f->fhocn && f->daidtt &&
+                   f->dvidtt, "cice_step_therm2_cleanup: NULL field");
+  const bool resident = f->state_resident != 0;
+  CICE_REQUIRE(!resident || therm2_state_,
+               "cice_step_therm2_cleanup: state_resident needs a cice_step_therm2_itd call on this batch in front");
+  hipStream_t s = stream_;
+  therm2_state_ = false;
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_;
+  const int ntr = ip->ntrcr;
+  enum { C_AICE = 0, C_AICE0, C_VICE, C_VSNO, C_EICE, C_ESNO, C_FRESH, C_FSALT, C_FHOCN, C_DAIDTT, C_DVIDTT, C_TRCR,
+         C_PLANES = C_TRCR + NTRCR };
+  if (clean_b_.n < C_PLANES * n2) clean_b_.alloc(C_PLANES * n2);
+  if (clean_bi_.n < n2) clean_bi_.alloc(n2);
+  clean_w_.alloc((size_t)nb_ * CW_WORDS);
+  const bool timed = clean_timed_;
+  for (hipEvent_t& e : clean_ev_)
+    if (timed && !e) CICE_HIP(hipEventCreate(&e));
+  auto d2 = [&](int k) { return clean_b_.p + (size_t)k * n2; };
+  fan_->fork(s);
+  if (!resident) {
+    aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
+    eicen_.upload(f->eicen, cs()); esnon_.upload(f->esnon, cs());
+    for (int it = 0; it < ntr; ++it) tracer_copy(it, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
+  }
+  {
+    const double* in2[5] = {f->fresh, f->fsalt, f->fhocn, f->daidtt, f->dvidtt};
+    for (int k = 0; k < 5; ++k) CICE_HIP(hipMemcpyAsync(d2(C_FRESH + k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+    CICE_HIP(hipMemcpyAsync(clean_bi_.p, f->tmask, n2 * 4, hipMemcpyHostToDevice, cs()));
+  }
+  fan_->join();
+  CICE_HIP(hipMemsetAsync(clean_w_.p, 0, clean_w_.n * 8, s));
+  CleanArgs a{};
+  a.p = *ip;
+  a.nx = nx_; a.ny = ny_; a.nblocks = nb_; a.blk = blk_.p; a.limit_aice = 1; a.dt = dt;
+  a.aicen = aicen_.p; a.trcrn = trcrn_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.eicen = eicen_.p; a.esnon = esnon_.p;
+  a.aice = d2(C_AICE); a.aice0 = d2(C_AICE0); a.fresh = d2(C_FRESH); a.fsalt = d2(C_FSALT); a.fhocn = d2(C_FHOCN);
+  a.bw = clean_w_.p; a.tmask = clean_bi_.p;
+  a.vice = d2(C_VICE); a.vsno = d2(C_VSNO); a.eice = d2(C_EICE); a.esno = d2(C_ESNO); a.trcr = d2(C_TRCR);
+  a.daidtt = d2(C_DAIDTT); a.dvidtt = d2(C_DVIDTT);
+  // stage 1: cleanup_itd on every block
+  clean_launch_all(a, s, timed ? clean_ev_ : nullptr);
+  std::vector<unsigned long long> w((size_t)nb_ * CW_WORDS);
+  CICE_HIP(hipMemcpyAsync(w.data(), clean_w_.p, w.size() * 8, hipMemcpyDeviceToHost, s));
+  CICE_HIP(hipStreamSynchronize(s));
+  clear_stop(l_stop, istop, jstop);
+  *bstop = 0; *stage = 0;
+  for (int b = 0; b < nb_; ++b) {
+    size_t q = 0;
+    if (!clean_decode(w.data() + (size_t)b * CW_WORDS, np, &q)) continue;
+    // the failing block as cleanup_itd leaves it, the blocks in front of it cleaned, the blocks behind it as they went in
+    *l_stop = 1; *stage = 1; *bstop = b + 1;
+    *istop = (int32_t)(q % nx_) + 1; *jstop = (int32_t)(q / nx_) + 1;
+    const size_t m = (size_t)b + 1;
+    auto part = [&](double* h, const double* d, size_t per) {
+      CICE_HIP(hipMemcpyAsync(h, d, m * per * np * 8, hipMemcpyDeviceToHost, cs()));
+    };
+    fan_->fork(s);
+    part(f->aicen, aicen_.p, NCAT); part(f->vicen, vicen_.p, NCAT); part(f->vsnon, vsnon_.p, NCAT);
+    part(f->eicen, eicen_.p, NCAT * NILYR); part(f->esnon, esnon_.p, NCAT * NSLYR);
+    for (int it = 0; it < ntr; ++it)
+      CICE_HIP(hipMemcpy2DAsync(f->trcrn + (size_t)it * np, (size_t)NTRCR * np * 8, trcrn_.p + (size_t)it * np,
+                                (size_t)NTRCR * np * 8, np * 8, (size_t)NCAT * m, hipMemcpyDeviceToHost, cs()));
+    part(f->fresh, d2(C_FRESH), 1); part(f->fsalt, d2(C_FSALT), 1); part(f->fhocn, d2(C_FHOCN), 1);
+    fan_->join();
+    CICE_HIP(hipStreamSynchronize(s));
+    return;
+  }
+  // stage 2: bound_state (ice_state.F90:162-217), the six updates of the transport on the batch's arrays.  The Halo
+  // addresses a level's blocks together, the batch keeps a block's levels together: with more than one block an array
+  // is turned over into clean_t_ and back.
+  if (halo) {
+    struct { DevBuf<double>* d; int levels; } arr[6] = {{&aicen_, NCAT}, {&trcrn_, NCAT * NTRCR}, {&vicen_, NCAT},
+                                                        {&vsnon_, NCAT}, {&eicen_, NCAT * NILYR}, {&esnon_, NCAT * NSLYR}};
+    if (nb_ > 1 && clean_t_.n < (size_t)NCAT * NTRCR * n2) clean_t_.alloc((size_t)NCAT * NTRCR * n2);
+    for (const auto& x : arr) {
+      double* base = x.d->p;
+      if (nb_ > 1) {
+        clean_launch_transpose(x.d->p, clean_t_.p, np, x.levels, nb_, true, s);
+        base = clean_t_.p;
+      }
+      if (x.d == &trcrn_) {
+        for (int c = 0; c < NCAT; ++c)   // trcrn(:,:,1:ntrcr,:,:) only (:206)
+          halo->update_r8(base + (size_t)c * NTRCR * n2, ntr, n2, true, LOC_CENTER, KIND_SCALAR);
+      } else {
+        halo->update_r8(base, x.levels, n2, true, LOC_CENTER, KIND_SCALAR);
+      }
+      if (nb_ > 1) clean_launch_transpose(clean_t_.p, x.d->p, np, x.levels, nb_, false, s);
+    }
+  }
+  if (timed) CICE_HIP(hipEventRecord(clean_ev_[CLEAN_TIMES - 1], s));
+  // stage 3: aggregate and the tendencies
+  clean_launch_aggregate(a, s);
+  if (timed) CICE_HIP(hipEventRecord(clean_ev_[CLEAN_TIMES], s));
+  fan_->fork(s);
+  aicen_.download(f->aicen, cs()); vicen_.download(f->vicen, cs()); vsnon_.download(f->vsnon, cs());
+  eicen_.download(f->eicen, cs()); esnon_.download(f->esnon, cs());
+  for (int it = 0; it < ntr; ++it) {
+    tracer_copy(it, trcrn_.p, f->trcrn, hipMemcpyDeviceToHost);
+    CICE_HIP(hipMemcpy2DAsync(f->trcr + (size_t)it * np, (size_t)NTRCR * np * 8, d2(C_TRCR) + (size_t)it * np,
+                              (size_t)NTRCR * np * 8, np * 8, (size_t)nb_, hipMemcpyDeviceToHost, cs()));
+  }
+  double* out2[11] = {f->aice, f->aice0, f->vice, f->vsno, f->eice, f->esno, f->fresh, f->fsalt, f->fhocn, f->daidtt,
+                      f->dvidtt};
+  for (int k = 0; k < 11; ++k) CICE_HIP(hipMemcpyAsync(out2[k], d2(k), n2 * 8, hipMemcpyDeviceToHost, cs()));
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < CLEAN_TIMES && timed; ++k) CICE_HIP(hipEventElapsedTime(&clean_ms_[k], clean_ev_[k], clean_ev_[k + 1]));
+  therm2_state_ = true;
+}
+
+void ColumnBatch::cleanup_times(bool enable, float ms[CLEAN_TIMES]) {
+  clean_timed_ = enable;
+  for (int k = 0; k < CLEAN_TIMES && ms; ++k) ms[k] = clean_ms_[k];
 }
 
 void ColumnBatch::itd_times(bool enable, float ms[4]) {

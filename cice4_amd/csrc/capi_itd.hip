@@ -274,6 +274,108 @@ int cice_step_therm2_itd(cice_ctx* ctx, double dt, double yday, const cice_therm
   CICE_CATCH
 }
 
+// cleanup_itd (ice_itd.F90:1600-1835) on one block: see include/cice4_amd.h and cleanup.h
+int cice_cleanup_itd(cice_ctx* ctx, int nx, int ny, int ilo, int ihi, int jlo, int jhi, double dt, int ntrcr, double* aicen,
+                     double* trcrn, double* vicen, double* vsnon, double* eicen, double* esnon, double* aice0, double* aice,
+                     const int32_t* trcr_depend, double* fresh, double* fsalt, double* fhocn, int heat_capacity,
+                     int32_t* l_stop, int32_t* istop, int32_t* jstop, int limit_aice) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(aicen && trcrn && vicen && vsnon && eicen && esnon && aice0 && aice && trcr_depend && l_stop && istop && jstop,
+               "cleanup_itd: NULL argument");
+  CICE_REQUIRE(nx >= 1 && ny >= 1 && ilo >= 1 && ihi <= nx && jlo >= 1 && jhi <= ny && dt > 0.0, "bad dimensions");
+  if (!heat_capacity) throw Error{CICE_EUNSUPPORTED, "cleanup_itd: heat_capacity = F (zerolayer_check) is not built"};
+  ItdBlock B(c_, nx, ny, 0, nullptr, nullptr);
+  B.set_tracers(ntrcr, trcr_depend);
+  hipStream_t s = c_->stream;
+  const int32_t blk[4] = {ilo, ihi, jlo, jhi};
+  CICE_HIP(hipMemcpyAsync(c_->itd_i.p + 7 * B.np, blk, 16, hipMemcpyHostToDevice, s));
+  CICE_HIP(hipStreamSynchronize(s));
+  const ItdState st{aicen, vicen, vsnon, trcrn, eicen, esnon};
+  B.state(st, ST_ALL, true);
+  B.up(IB_2D + I2_AICE, aice); B.up(IB_2D + I2_AICE0, aice0);
+  if (fresh) B.up(IB_2D + I2_FRESH, fresh);
+  if (fsalt) B.up(IB_2D + I2_FSALT, fsalt);
+  if (fhocn) B.up(IB_2D + I2_FHOCN, fhocn);
+  static_assert(ITD_REC_WORDS >= CW_WORDS, "the record words hold a block's words");
+  B.clear_rec();
+  CleanArgs a{};
+  a.p = B.a.p;
+  a.nx = nx; a.ny = ny; a.nblocks = 1; a.blk = B.a.blk; a.limit_aice = limit_aice != 0; a.dt = dt;
+  a.aicen = B.a.aicen; a.trcrn = B.a.trcrn; a.vicen = B.a.vicen; a.vsnon = B.a.vsnon; a.eicen = B.a.eicen;
+  a.esnon = B.a.esnon; a.aice = B.a.aice; a.aice0 = B.a.aice0;
+  a.fresh = fresh ? B.a.fresh : nullptr; a.fsalt = fsalt ? B.a.fsalt : nullptr; a.fhocn = fhocn ? B.a.fhocn : nullptr;
+  a.bw = c_->itd_rec.p;
+  clean_launch_all(a, s);
+  B.state(st, ST_ALL, false);
+  B.down(aice, IB_2D + I2_AICE); B.down(aice0, IB_2D + I2_AICE0);
+  if (fresh) B.down(fresh, IB_2D + I2_FRESH);
+  if (fsalt) B.down(fsalt, IB_2D + I2_FSALT);
+  if (fhocn) B.down(fhocn, IB_2D + I2_FHOCN);
+  unsigned long long r[ITD_REC_WORDS];
+  itd_read_rec(c_, r);
+  clear_stop(l_stop, istop, jstop);
+  size_t q = 0;
+  if (clean_decode(r, B.np, &q)) {
+    *l_stop = 1; *istop = (int32_t)(q % nx) + 1; *jstop = (int32_t)(q / nx) + 1;
+  }
+  CICE_CATCH
+}
+
+// aggregate (ice_itd.F90:279-485) on one block
+int cice_aggregate(cice_ctx* ctx, int nx, int ny, const double* aicen, const double* trcrn, const double* vicen,
+                   const double* vsnon, const double* eicen, const double* esnon, double* aice, double* trcr, double* vice,
+                   double* vsno, double* eice, double* esno, double* aice0, const int32_t* tmask, int ntrcr,
+                   const int32_t* trcr_depend) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(aicen && trcrn && vicen && vsnon && eicen && esnon && aice && trcr && vice && vsno && eice && esno && aice0 &&
+                   tmask && trcr_depend, "aggregate: NULL argument");
+  ItdBlock B(c_, nx, ny, 0, nullptr, nullptr);
+  B.set_tracers(ntrcr, trcr_depend);
+  hipStream_t s = c_->stream;
+  auto in = [](const double* p) { return const_cast<double*>(p); };   // (uploaded only)
+  const ItdState st{in(aicen), in(vicen), in(vsnon), in(trcrn), in(eicen), in(esnon)};
+  B.state(st, ST_ALL, true);
+  int32_t* dmask = c_->itd_i.p + B.np;
+  CICE_HIP(hipMemcpyAsync(dmask, tmask, B.np * 4, hipMemcpyHostToDevice, s));
+  CICE_HIP(hipMemcpyAsync(B.pl(IB_SHIFT + 4), trcr, (size_t)NTRCR * B.np * 8, hipMemcpyHostToDevice, s));   // planes >= ntrcr stay
+  CleanArgs a{};
+  a.p = B.a.p;
+  a.nx = nx; a.ny = ny; a.nblocks = 1; a.blk = B.a.blk; a.dt = 1.0;
+  a.aicen = B.a.aicen; a.trcrn = B.a.trcrn; a.vicen = B.a.vicen; a.vsnon = B.a.vsnon; a.eicen = B.a.eicen;
+  a.esnon = B.a.esnon; a.aice = B.a.aice; a.aice0 = B.a.aice0; a.tmask = dmask;
+  a.vice = B.pl(IB_SHIFT); a.vsno = B.pl(IB_SHIFT + 1); a.eice = B.pl(IB_SHIFT + 2); a.esno = B.pl(IB_SHIFT + 3);
+  a.trcr = B.pl(IB_SHIFT + 4);
+  clean_launch_aggregate(a, s);
+  B.down(aice, IB_2D + I2_AICE); B.down(aice0, IB_2D + I2_AICE0);
+  B.down(vice, IB_SHIFT); B.down(vsno, IB_SHIFT + 1); B.down(eice, IB_SHIFT + 2); B.down(esno, IB_SHIFT + 3);
+  B.down(trcr, IB_SHIFT + 4, NTRCR);
+  CICE_HIP(hipStreamSynchronize(s));
+  CICE_CATCH
+}
+
+// The second half of step_therm2 on the batch (ice_step_mod.F90:445-511): see include/cice4_amd.h
+int cice_step_therm2_cleanup(cice_ctx* ctx, double dt, const cice_therm2_cleanup_fields* f, int32_t* l_stop, int32_t* istop,
+                             int32_t* jstop, int32_t* bstop, int32_t* stage) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(f && l_stop && istop && jstop && bstop && stage, "NULL argument");
+  if (f->ncat == 1) throw Error{CICE_EUNSUPPORTED, "cice_step_therm2_cleanup: ncat = 1 is not built"};
+  CICE_REQUIRE(f->ncat == NCAT, "cice_step_therm2_cleanup: ncat is not the library's");
+  NEED_BATCH(true);
+  Halo* halo = nullptr;
+  if (f->bound) {
+    CICE_REQUIRE(c_->have_domain, "cice_step_therm2_cleanup: bound = 1 needs cice_domain_create");
+    CICE_REQUIRE(c_->batch.same_layout(c_->dom), "cice_step_therm2_cleanup: the batch does not have the domain's layout");
+    c_->need_halo();
+    halo = c_->halo.get();
+  }
+  c_->batch.step_therm2_cleanup(c_->itd(), dt, f, halo, l_stop, istop, jstop, bstop, stage);
+  CICE_CATCH
+}
+
+int cice_therm2_cleanup_times(cice_ctx* ctx, int enable, float ms[12]) {
+  CICE_TRY(ctx) c_->batch.cleanup_times(enable != 0, ms); CICE_CATCH
+}
+
 int cice_therm2_itd_times(cice_ctx* ctx, int enable, float ms[4]) {
   CICE_TRY(ctx) c_->batch.itd_times(enable != 0, ms); CICE_CATCH
 }

@@ -525,6 +525,48 @@ module cice4_amd_c
       end function
    end interface
 
+   ! the second half of step_therm2 (source/ice_step_mod.F90:445-511; cice4_amd/csrc/cleanup.hip)
+   type, bind(C) :: cice_therm2_cleanup_fields
+      integer(c_int) :: ncat, state_resident, bound
+      type(c_ptr) :: aicen, trcrn, vicen, vsnon, eicen, esnon
+      type(c_ptr) :: tmask
+      type(c_ptr) :: aice, aice0, vice, vsno, eice, esno, trcr
+      type(c_ptr) :: fresh, fsalt, fhocn, daidtt, dvidtt
+   end type
+
+   interface
+      ! fresh, fsalt, fhocn: c_loc of the array, or c_null_ptr for an absent optional
+      integer(c_int) function cice_cleanup_itd(ctx, nx_block, ny_block, ilo, ihi, jlo, jhi, dt, ntrcr, aicen, trcrn, vicen, &
+            vsnon, eicen, esnon, aice0, aice, trcr_depend, fresh, fsalt, fhocn, heat_capacity, l_stop, istop, jstop, &
+            limit_aice) bind(C, name='cice_cleanup_itd')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, ilo, ihi, jlo, jhi, ntrcr, heat_capacity, limit_aice
+         real(c_double), value :: dt
+         real(c_double), intent(inout) :: aicen(*), trcrn(*), vicen(*), vsnon(*), eicen(*), esnon(*), aice0(*), aice(*)
+         integer(c_int), intent(in) :: trcr_depend(*)
+         type(c_ptr), value :: fresh, fsalt, fhocn
+         integer(c_int), intent(out) :: l_stop, istop, jstop
+      end function
+      integer(c_int) function cice_aggregate(ctx, nx_block, ny_block, aicen, trcrn, vicen, vsnon, eicen, esnon, aice, trcr, &
+            vice, vsno, eice, esno, aice0, tmask, ntrcr, trcr_depend) bind(C, name='cice_aggregate')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, ntrcr
+         real(c_double), intent(in) :: aicen(*), trcrn(*), vicen(*), vsnon(*), eicen(*), esnon(*)
+         real(c_double), intent(inout) :: aice(*), trcr(*), vice(*), vsno(*), eice(*), esno(*), aice0(*)
+         integer(c_int), intent(in) :: tmask(*), trcr_depend(*)
+      end function
+      integer(c_int) function cice_step_therm2_cleanup(ctx, dt, f, l_stop, istop, jstop, bstop, stage) &
+            bind(C, name='cice_step_therm2_cleanup')
+         import
+         type(c_ptr), value :: ctx
+         real(c_double), value :: dt
+         type(cice_therm2_cleanup_fields), intent(in) :: f
+         integer(c_int), intent(out) :: l_stop, istop, jstop, bstop, stage
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

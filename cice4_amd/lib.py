@@ -104,6 +104,15 @@ class Therm2Fields(C.Structure):
     _fields_ = [("ncat", C.c_int), ("kitd", C.c_int), ("state_resident", C.c_int)] + [(n, C.c_void_p) for n in THERM2_PTRS]
 
 
+CLEANUP_PTRS = ("aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "tmask", "aice", "aice0", "vice", "vsno", "eice", "esno",
+                "trcr", "fresh", "fsalt", "fhocn", "daidtt", "dvidtt")
+CLEANUP_TIMES = ("head",) + tuple(f"pass{p}" for p in range(1, 9)) + ("zap", "bound_state", "aggregate")
+
+
+class Therm2CleanupFields(C.Structure):
+    _fields_ = [("ncat", C.c_int), ("state_resident", C.c_int), ("bound", C.c_int)] + [(n, C.c_void_p) for n in CLEANUP_PTRS]
+
+
 class ThermoFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in THERMO_STATE + THERMO_FORCING + THERMO_CAT_IN + THERMO_SW
                 + THERMO_OUT + THERMO_ONSET]
@@ -830,6 +839,47 @@ class Context:
         self._ck(self.lib.cice_step_therm2_itd(self.h, C.c_double(dt), C.c_double(yday), C.byref(f),
                                                *[C.byref(x) for x in st]))
         return dict(zip(("l_stop", "istop", "jstop", "bstop", "stage"), (x.value for x in st)))
+
+    # ---- the second half of step_therm2: cleanup_itd, bound_state, aggregate ------
+    def cleanup_itd(self, ilo, ihi, jlo, jhi, dt, a, limit_aice=True, heat_capacity=True, fluxes=("fresh", "fsalt", "fhocn")):
+        """cice_cleanup_itd on one block.  a: aicen, vicen, vsnon (ncat,ny,nx), trcrn (ncat,5,ny,nx), eicen, esnon, aice0,
+        aice and the fluxes named in `fluxes` (the others are absent optionals); updated in place.
+        Returns (l_stop, istop, jstop)."""
+        ny, nx = a["aice"].shape
+        ntr, dep = self._itd
+        st = [C.c_int32(0) for _ in range(3)]
+        self._ck(self.lib.cice_cleanup_itd(
+            self.h, nx, ny, ilo, ihi, jlo, jhi, C.c_double(dt), ntr,
+            *[_f8(a[k]) for k in ("aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "aice0", "aice")], _i4(dep),
+            *[_f8(a[k]) if k in fluxes else None for k in ("fresh", "fsalt", "fhocn")], int(heat_capacity),
+            *[C.byref(x) for x in st], int(limit_aice)))
+        return tuple(x.value for x in st)
+
+    def aggregate(self, a):
+        """cice_aggregate on one block.  a: the state and tmask (int32) in; aice, trcr (5,ny,nx), vice, vsno, eice, esno,
+        aice0 out."""
+        ny, nx = a["aice"].shape
+        ntr, dep = self._itd
+        self._ck(self.lib.cice_aggregate(
+            self.h, nx, ny, *[_f8(a[k]) for k in ("aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "aice", "trcr", "vice",
+                                                  "vsno", "eice", "esno", "aice0")], _i4(a["tmask"]), ntr, _i4(dep)))
+
+    def step_therm2_cleanup(self, dt, a, state_resident=False, bound=False):
+        """cice_step_therm2_cleanup on the batch (thermo_batch_alloc).  a: the arrays of CLEANUP_PTRS ((nb, ...)).
+        Returns dict(l_stop, istop, jstop, bstop, stage)."""
+        f = Therm2CleanupFields()
+        f.ncat, f.state_resident, f.bound = NCAT, int(state_resident), int(bound)
+        for n in CLEANUP_PTRS:
+            setattr(f, n, _i4(a[n]) if n == "tmask" else _f8(a[n]))
+        st = [C.c_int32(0) for _ in range(5)]
+        self._ck(self.lib.cice_step_therm2_cleanup(self.h, C.c_double(dt), C.byref(f), *[C.byref(x) for x in st]))
+        return dict(zip(("l_stop", "istop", "jstop", "bstop", "stage"), (x.value for x in st)))
+
+    def therm2_cleanup_times(self, enable=True):
+        """cice_therm2_cleanup_times: switch the event timing on / off; the times (ms) of the last timed call by CLEANUP_TIMES"""
+        ms = (C.c_float * len(CLEANUP_TIMES))()
+        self._ck(self.lib.cice_therm2_cleanup_times(self.h, int(enable), ms))
+        return dict(zip(CLEANUP_TIMES, ms))
 
     def therm2_itd_times(self, enable=True):
         """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""

@@ -508,9 +508,11 @@ int cice_frzmlt_bottom_lateral(cice_ctx *ctx, int nx_block, int ny_block, int il
 
 /* ---- thermodynamic changes of the thickness distribution (source/ice_therm_itd.F90): the first half of step_therm2,
  * source/ice_step_mod.F90:286-422 -- rain, aggregate_area, linear_itd, add_new_ice, lateral_melt -- on the device.
- * cleanup_itd, bound_state, aggregate, ridging and shortwave stay with the caller.  No transcendental function on this
- * path: results are those of the reference bit for bit (tests/test_gpu_therm_itd.py, tests/golden/therm_itd.npz; the
- * "auscom" flavour compiles the same kernels with its own constants and has no parity fixture yet).
+ * The second half (:445-511) -- cleanup_itd, bound_state, aggregate, the tendencies -- follows below
+ * (cice_step_therm2_cleanup); ridging and shortwave stay with the caller.  No transcendental function on this
+ * path: results are those of the reference bit for bit (tests/test_gpu_therm_itd.py, tests/golden/therm_itd.npz,
+ * tests/test_gpu_cleanup_itd.py, tests/golden/cleanup_itd.npz; the "auscom" flavour compiles the same kernels with its
+ * own constants and has no parity fixture yet).
  * cice_itd_init: call it after init_itd (source/ice_itd.F90:94) with the module variables the routines read:
  * ntrcr, trcr_depend (ice_state), the tracer slots, tr_iage (ice_age), tr_lvl (ice_mechred), update_ocn_f (ice_flux),
  * hin_max(0:ncat) and hi_min (ice_itd). */
@@ -589,6 +591,54 @@ int cice_step_therm2_itd(cice_ctx *ctx, double dt, double yday, const cice_therm
  * calls record HIP events around their kernels; ms (may be NULL) receives the device times (ms) of the last call that
  * did: rain + aggregate_area, linear_itd, add_new_ice, lateral_melt. */
 int cice_therm2_itd_times(cice_ctx *ctx, int enable, float ms[4]);
+
+/* ---- the second half of step_therm2 (source/ice_step_mod.F90:445-511) on the device ----
+ * cleanup_itd (source/ice_itd.F90:1600-1835: aggregate_area, the bounds check, rebin, zap_small_areas, the flux update),
+ * one block, host pointers, the reference's argument order.  fresh / fsalt / fhocn may each be NULL (an absent optional).
+ * heat_capacity = 0 (zerolayer_check) is CICE_EUNSUPPORTED.  limit_aice = 0 skips the bounds check and the zap
+ * (limit_aice_in = .false.).  Stops, each with the arrays as the reference leaves them:
+ *   aggregate area out of bounds: the LAST failing cell, j then i; only aice, aice0 have been written;
+ *   shift_ice out of rebin (a donor with negative volume; no fixture): the LAST such cell of the first pass that has
+ *     one; the lift of category 1 and the passes in front of it have been applied;
+ *   negative area in zap_small_areas: the FIRST cell of the FIRST category with aicen < -puny; the categories in front
+ *     of it are zapped, the fluxes are untouched. */
+int cice_cleanup_itd(cice_ctx *ctx, int nx_block, int ny_block, int ilo, int ihi, int jlo, int jhi, double dt, int ntrcr,
+                     double *aicen, double *trcrn, double *vicen, double *vsnon, double *eicen, double *esnon,
+                     double *aice0, double *aice, const int32_t *trcr_depend, double *fresh, double *fsalt,
+                     double *fhocn, int heat_capacity, int32_t *l_stop, int32_t *istop, int32_t *jstop, int limit_aice);
+/* aggregate (source/ice_itd.F90:279-485), one block, every cell of it; trcr is (nx,ny,max_ntrcr), its first ntrcr planes
+ * are written. */
+int cice_aggregate(cice_ctx *ctx, int nx_block, int ny_block, const double *aicen, const double *trcrn,
+                   const double *vicen, const double *vsnon, const double *eicen, const double *esnon, double *aice,
+                   double *trcr, double *vice, double *vsno, double *eice, double *esno, double *aice0,
+                   const int32_t *tmask, int ntrcr, const int32_t *trcr_depend);
+/* The half as ONE call on the batch, all blocks: stage 1 cleanup_itd (limit_aice = T) on the physical cells of every
+ * block, 2 bound_state (source/ice_state.F90:162-217; cannot stop), 3 aggregate on every cell of every block and
+ * daidtt = (aice - daidtt)/dt, dvidtt = (vice - dvidtt)/dt.  Shapes as in cice_thermo_fields; trcr (nx,ny,max_ntrcr,nb).
+ * state_resident = 1: the state with all its ntrcr tracer planes is what cice_step_therm2_itd left on the device; the
+ *   host arrays are the download targets and must hold what that call downloaded.  CICE_EINVAL unless the last call that
+ *   touched the batch's state was a cice_step_therm2_itd (or a cice_step_therm2_cleanup) that did not stop.
+ * state_resident = 0: the state is uploaded.
+ * bound = 1: the ghost-cell update runs on the context's domain (CICE_EINVAL without one, or if the batch does not have
+ *   its layout).  bound = 0: it is skipped and aggregate sees the ghost cells as they are -- for a caller with its own
+ *   boundary code.
+ * fresh, fsalt, fhocn, daidtt, dvidtt are uploaded and downloaded; aice ... trcr are written.  One download at the end.
+ * Stops: *stage = 1, *bstop the block (1-based), (istop, jstop) the cell.  The failing block holds what
+ * cice_cleanup_itd leaves (state and fluxes), the blocks in front of it have completed stage 1, the blocks behind it
+ * come back as they went in; stages 2 and 3 have not run, aice ... trcr, daidtt, dvidtt are untouched.
+ * ncat must be CICE_NCAT; ncat = 1 is CICE_EUNSUPPORTED. */
+typedef struct {
+  int ncat, state_resident, bound;
+  double *aicen, *trcrn, *vicen, *vsnon, *eicen, *esnon;
+  const int32_t *tmask;
+  double *aice, *aice0, *vice, *vsno, *eice, *esno, *trcr; /* out */
+  double *fresh, *fsalt, *fhocn, *daidtt, *dvidtt;         /* in / out */
+} cice_therm2_cleanup_fields;
+int cice_step_therm2_cleanup(cice_ctx *ctx, double dt, const cice_therm2_cleanup_fields *f, int32_t *l_stop,
+                             int32_t *istop, int32_t *jstop, int32_t *bstop, int32_t *stage);
+/* Measurement aid (scripts/therm2_cleanup_cost.py), off by default, as cice_therm2_itd_times: the device times (ms) of
+ * the last timed cice_step_therm2_cleanup: head, the eight passes of rebin, zap, bound_state, aggregate. */
+int cice_therm2_cleanup_times(cice_ctx *ctx, int enable, float ms[12]);
 
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
