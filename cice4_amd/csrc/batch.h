@@ -11,6 +11,7 @@
 #include "domain.h"
 #include "halo.h"
 #include "itd.h"
+#include "ridge.h"
 #include "therm.h"
 
 namespace cice {
@@ -24,6 +25,8 @@ enum { A_AICEN = 0, A_TRCRN = 1, A_VICEN = A_TRCRN + NTRCR, A_VSNON, A_EICEN, A_
 // the (nx, ny[, nblocks]) fields of the thickness-distribution stage in the order they are staged
 // device times of cice_therm2_cleanup_times: head, the eight passes, zap, bound_state, aggregate
 enum { CLEAN_TIMES = 12 };
+// device times of cice_ridge_times: rate kernel and shift kernel of each of the 20 possible iterations, the finish
+enum { RIDGE_TIMES = 2 * RIDGE_NITERMAX + 1 };
 enum { I2_AICE = 0, I2_AICE0, I2_FRAIN, I2_FRZMLT, I2_TF, I2_RSIDE, I2_FRESH, I2_FSALT, I2_FHOCN, I2_FRAZIL, I2_MELTL,
        I2_FRZ_ONSET };
 
@@ -97,6 +100,9 @@ class ColumnBatch {
   // halo: the context's ghost-cell update (bound = 1) or nullptr
   void step_therm2_cleanup(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, Halo* halo, int32_t* l_stop,
                            int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
+  void step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f, Halo* halo,
+                  int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
+  void ridge_times(bool enable, float ms[RIDGE_TIMES]);
   void set_option(const char* key, int value);      // before or after alloc; kept across re-allocations
   void itd_times(bool enable, float ms[4]);         // likewise
   void cleanup_times(bool enable, float ms[CLEAN_TIMES]);
@@ -119,6 +125,14 @@ class ColumnBatch {
   enum { MRG_UP = 1, MRG_RUN = 2, MRG_DOWN = 4, MRG_ALL = 7 };
   void merge_phases(const cice_merge_fields* f, const double* aicen_init_dev, bool atmo_on_device, int phases);
   void read_rec(unsigned long long h[ITD_REC_WORDS]);
+  // what cice_step_ridge has beyond the cleanup's fields
+  struct RidgeStage {
+    const RidgeParams* rp;
+    const double *rdg_conv, *rdg_shear;
+    double *dardg1dt, *dardg2dt, *dvirdgdt, *opening;
+  };
+  void column_stages(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, const RidgeStage* rs, Halo* halo,
+                     int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
 
   hipStream_t stream_ = nullptr;
   CopyFan* fan_ = nullptr;
@@ -149,6 +163,13 @@ class ColumnBatch {
   hipEvent_t clean_ev_[CLEAN_TIMES + 1] = {};
   bool clean_timed_ = false;
   float clean_ms_[CLEAN_TIMES] = {};
+  // ridging stage: work planes, rdg_conv / rdg_shear and the four diagnostics; the list; block words (ridge.h)
+  DevBuf<double> ridge_b_;
+  DevBuf<int32_t> ridge_bi_;
+  DevBuf<unsigned long long> ridge_w_;
+  hipEvent_t ridge_ev_[2 * RIDGE_QUEUE + 1] = {};
+  bool ridge_timed_ = false;
+  float ridge_ms_[RIDGE_TIMES] = {};
 };
 
 }  // namespace cice

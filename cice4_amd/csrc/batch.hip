@@ -43,6 +43,8 @@ ColumnBatch::~ColumnBatch() {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : clean_ev_)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ridge_ev_)
+    if (e) (void)hipEventDestroy(e);
 }
 
 // Every field of cice_thermo_fields, once, in the order the fields travel: what alloc sizes, upload and download move
@@ -467,6 +469,31 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
 // The second half of step_therm2 on the batch (ice_step_mod.F90:445-511): see include/cice4_amd.h and cleanup.h
 void ColumnBatch::step_therm2_cleanup(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, Halo* halo,
                                       int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage) {
+  column_stages(ip, dt, f, nullptr, halo, l_stop, istop, jstop, bstop, stage);
+}
+
+// The column half of step_dynamics on the batch (ice_step_mod.F90:586-745): ridge_ice in front of the same three stages
+void ColumnBatch::step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f, Halo* halo,
+                             int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage) {
+  CICE_REQUIRE(rp, "cice_ridge_init has not been called");
+  CICE_REQUIRE(f->rdg_conv && f->rdg_shear && f->dardg1dt && f->dardg2dt && f->dvirdgdt && f->opening,
+               "cice_step_ridge: NULL field");
+  cice_therm2_cleanup_fields c{};
+  c.ncat = f->ncat; c.state_resident = 0; c.bound = f->bound;
+  c.aicen = f->aicen; c.trcrn = f->trcrn; c.vicen = f->vicen; c.vsnon = f->vsnon; c.eicen = f->eicen; c.esnon = f->esnon;
+  c.tmask = f->tmask;
+  c.aice = f->aice; c.aice0 = f->aice0; c.vice = f->vice; c.vsno = f->vsno; c.eice = f->eice; c.esno = f->esno;
+  c.trcr = f->trcr;
+  c.fresh = f->fresh; c.fsalt = f->fsalt; c.fhocn = f->fhocn; c.daidtt = f->daidtd; c.dvidtt = f->dvidtd;
+  const RidgeStage rs{rp, f->rdg_conv, f->rdg_shear, f->dardg1dt, f->dardg2dt, f->dvirdgdt, f->opening};
+  column_stages(ip, dt, &c, &rs, halo, l_stop, istop, jstop, bstop, stage);
+}
+
+// cleanup_itd, bound_state, aggregate and the tendencies on the batch; with `rs`, ridge_ice (ridge.h) in front of them as
+// stage 1 on the physical tmask cells of every block that has one, and the numbers of the other stages one up
+void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, const RidgeStage* rs,
+                                Halo* halo, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop,
+                                int32_t* stage) {
   CICE_REQUIRE(ip, "cice_itd_init has not been called");
   CICE_REQUIRE(dt > 0.0, "dt");
   CICE_REQUIRE(f->aicen && f->trcrn && f->vicen && f->vsnon && f->eicen && f->esnon && f->tmask && f->aice && f->aice0 &&
@@ -499,7 +526,86 @@ void ColumnBatch::step_therm2_cleanup(const ItdParams* ip, double dt, const cice
     for (int k = 0; k < 5; ++k) CICE_HIP(hipMemcpyAsync(d2(C_FRESH + k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
     CICE_HIP(hipMemcpyAsync(clean_bi_.p, f->tmask, n2 * 4, hipMemcpyHostToDevice, cs()));
   }
+  enum { R_CONV = RG_PLANES, R_SHEAR, R_D1, R_D2, R_DV, R_OPEN, R_PLANES };
+  auto dr = [&](int k) { return ridge_b_.p + (size_t)k * n2; };
+  if (rs) {                            // ridge_ice reads aice0; its diagnostics keep what they held off the list
+    if (ridge_b_.n < R_PLANES * n2) ridge_b_.alloc(R_PLANES * n2);
+    if (ridge_bi_.n < n2) ridge_bi_.alloc(n2);
+    ridge_w_.alloc((size_t)nb_ * RW_WORDS);
+    const double* in[7] = {rs->rdg_conv, rs->rdg_shear, rs->dardg1dt, rs->dardg2dt, rs->dvirdgdt, rs->opening, f->aice0};
+    for (int k = 0; k < 6; ++k) CICE_HIP(hipMemcpyAsync(dr(R_CONV + k), in[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+    CICE_HIP(hipMemcpyAsync(d2(C_AICE0), in[6], n2 * 8, hipMemcpyHostToDevice, cs()));
+  }
   fan_->join();
+  clear_stop(l_stop, istop, jstop);
+  *bstop = 0; *stage = 0;
+  const int s0 = rs ? 1 : 0;           // what the stage numbers of the cleanup are shifted by
+  // the blocks 0 .. b of the state and of the named planes: what a stop in block b hands back
+  auto part_state = [&](int b) {
+    const size_t m = (size_t)b + 1;
+    auto part = [&](double* h, const double* d, size_t per) {
+      CICE_HIP(hipMemcpyAsync(h, d, m * per * np * 8, hipMemcpyDeviceToHost, cs()));
+    };
+    part(f->aicen, aicen_.p, NCAT); part(f->vicen, vicen_.p, NCAT); part(f->vsnon, vsnon_.p, NCAT);
+    part(f->eicen, eicen_.p, NCAT * NILYR); part(f->esnon, esnon_.p, NCAT * NSLYR);
+    for (int it = 0; it < ntr; ++it)
+      CICE_HIP(hipMemcpy2DAsync(f->trcrn + (size_t)it * np, (size_t)NTRCR * np * 8, trcrn_.p + (size_t)it * np,
+                                (size_t)NTRCR * np * 8, np * 8, (size_t)NCAT * m, hipMemcpyDeviceToHost, cs()));
+  };
+  if (rs) {
+    CICE_HIP(hipMemsetAsync(ridge_w_.p, 0, ridge_w_.n * 8, s));
+    ridge_launch_list(ridge_bi_.p, clean_bi_.p, blk_.p, nx_, ny_, nb_, s);
+    RidgeArgs r{};
+    r.p = *ip; r.r = *rs->rp;
+    r.nx = nx_; r.ny = ny_; r.nblocks = nb_; r.listpos = ridge_bi_.p; r.dt = dt;
+    r.rdg_conv = dr(R_CONV); r.rdg_shear = dr(R_SHEAR);
+    r.aicen = aicen_.p; r.trcrn = trcrn_.p; r.vicen = vicen_.p; r.vsnon = vsnon_.p; r.eicen = eicen_.p; r.esnon = esnon_.p;
+    r.aice0 = d2(C_AICE0);
+    r.dardg1dt = dr(R_D1); r.dardg2dt = dr(R_D2); r.dvirdgdt = dr(R_DV); r.opening = dr(R_OPEN);
+    r.fresh = d2(C_FRESH); r.fhocn = d2(C_FHOCN);
+    r.work = dr(0); r.bw = ridge_w_.p;
+    const bool rtimed = ridge_timed_;
+    for (hipEvent_t& e : ridge_ev_)
+      if (rtimed && !e) CICE_HIP(hipEventCreate(&e));
+    for (float& x : ridge_ms_) x = 0.0f;
+    std::vector<unsigned long long> rw((size_t)nb_ * RW_WORDS);
+    for (int done = 0;;) {
+      const int count = std::min<int>(RIDGE_QUEUE, RIDGE_NITERMAX - done);
+      ridge_launch_iterations(r, done + 1, count, s, rtimed ? ridge_ev_ : nullptr);
+      CICE_HIP(hipMemcpyAsync(rw.data(), ridge_w_.p, rw.size() * 8, hipMemcpyDeviceToHost, s));
+      CICE_HIP(hipStreamSynchronize(s));
+      for (int k = 0; k < 2 * count && rtimed; ++k)
+        CICE_HIP(hipEventElapsedTime(&ridge_ms_[2 * done + k], ridge_ev_[k], ridge_ev_[k + 1]));
+      done += count;
+      bool more = false;
+      for (int b = 0; b < nb_; ++b) more = more || ridge_wants_more(rw.data() + (size_t)b * RW_WORDS, done);
+      if (!more) break;
+    }
+    if (rtimed) CICE_HIP(hipEventRecord(ridge_ev_[0], s));
+    ridge_launch_finish(r, s);         // (leaves a stopped block alone)
+    if (rtimed) {
+      CICE_HIP(hipEventRecord(ridge_ev_[1], s));
+      CICE_HIP(hipStreamSynchronize(s));
+      CICE_HIP(hipEventElapsedTime(&ridge_ms_[RIDGE_TIMES - 1], ridge_ev_[0], ridge_ev_[1]));
+    }
+    for (int b = 0; b < nb_; ++b) {
+      unsigned pos = 0;
+      int n_it = 0;
+      if (!ridge_decode(rw.data() + (size_t)b * RW_WORDS, &pos, &n_it)) continue;
+      // the failing block as ridge_ice leaves it, the blocks in front of it ridged, the blocks behind it as they went in
+      *l_stop = 1; *stage = 1; *bstop = b + 1;
+      if (pos) { *istop = (int32_t)((pos - 1) % nx_) + 1; *jstop = (int32_t)((pos - 1) / nx_) + 1; }
+      const size_t m = (size_t)b + 1;
+      fan_->fork(s);
+      part_state(b);
+      double* h[7] = {rs->dardg1dt, rs->dardg2dt, rs->dvirdgdt, rs->opening, f->aice0, f->fresh, f->fhocn};
+      const double* d[7] = {dr(R_D1), dr(R_D2), dr(R_DV), dr(R_OPEN), d2(C_AICE0), d2(C_FRESH), d2(C_FHOCN)};
+      for (int k = 0; k < 7; ++k) CICE_HIP(hipMemcpyAsync(h[k], d[k], m * np * 8, hipMemcpyDeviceToHost, cs()));
+      fan_->join();
+      CICE_HIP(hipStreamSynchronize(s));
+      return;
+    }
+  }
   CICE_HIP(hipMemsetAsync(clean_w_.p, 0, clean_w_.n * 8, s));
   CleanArgs a{};
   a.p = *ip;
@@ -514,25 +620,17 @@ void ColumnBatch::step_therm2_cleanup(const ItdParams* ip, double dt, const cice
   std::vector<unsigned long long> w((size_t)nb_ * CW_WORDS);
   CICE_HIP(hipMemcpyAsync(w.data(), clean_w_.p, w.size() * 8, hipMemcpyDeviceToHost, s));
   CICE_HIP(hipStreamSynchronize(s));
-  clear_stop(l_stop, istop, jstop);
-  *bstop = 0; *stage = 0;
   for (int b = 0; b < nb_; ++b) {
     size_t q = 0;
     if (!clean_decode(w.data() + (size_t)b * CW_WORDS, np, &q)) continue;
     // the failing block as cleanup_itd leaves it, the blocks in front of it cleaned, the blocks behind it as they went in
-    *l_stop = 1; *stage = 1; *bstop = b + 1;
+    *l_stop = 1; *stage = 1 + s0; *bstop = b + 1;
     *istop = (int32_t)(q % nx_) + 1; *jstop = (int32_t)(q / nx_) + 1;
     const size_t m = (size_t)b + 1;
-    auto part = [&](double* h, const double* d, size_t per) {
-      CICE_HIP(hipMemcpyAsync(h, d, m * per * np * 8, hipMemcpyDeviceToHost, cs()));
-    };
     fan_->fork(s);
-    part(f->aicen, aicen_.p, NCAT); part(f->vicen, vicen_.p, NCAT); part(f->vsnon, vsnon_.p, NCAT);
-    part(f->eicen, eicen_.p, NCAT * NILYR); part(f->esnon, esnon_.p, NCAT * NSLYR);
-    for (int it = 0; it < ntr; ++it)
-      CICE_HIP(hipMemcpy2DAsync(f->trcrn + (size_t)it * np, (size_t)NTRCR * np * 8, trcrn_.p + (size_t)it * np,
-                                (size_t)NTRCR * np * 8, np * 8, (size_t)NCAT * m, hipMemcpyDeviceToHost, cs()));
-    part(f->fresh, d2(C_FRESH), 1); part(f->fsalt, d2(C_FSALT), 1); part(f->fhocn, d2(C_FHOCN), 1);
+    part_state(b);
+    double* h[3] = {f->fresh, f->fsalt, f->fhocn};
+    for (int k = 0; k < 3; ++k) CICE_HIP(hipMemcpyAsync(h[k], d2(C_FRESH + k), m * np * 8, hipMemcpyDeviceToHost, cs()));
     fan_->join();
     CICE_HIP(hipStreamSynchronize(s));
     return;
@@ -574,10 +672,19 @@ void ColumnBatch::step_therm2_cleanup(const ItdParams* ip, double dt, const cice
   double* out2[11] = {f->aice, f->aice0, f->vice, f->vsno, f->eice, f->esno, f->fresh, f->fsalt, f->fhocn, f->daidtt,
                       f->dvidtt};
   for (int k = 0; k < 11; ++k) CICE_HIP(hipMemcpyAsync(out2[k], d2(k), n2 * 8, hipMemcpyDeviceToHost, cs()));
+  if (rs) {
+    double* h[4] = {rs->dardg1dt, rs->dardg2dt, rs->dvirdgdt, rs->opening};
+    for (int k = 0; k < 4; ++k) CICE_HIP(hipMemcpyAsync(h[k], dr(R_D1 + k), n2 * 8, hipMemcpyDeviceToHost, cs()));
+  }
   fan_->join();
   CICE_HIP(hipStreamSynchronize(s));
   for (int k = 0; k < CLEAN_TIMES && timed; ++k) CICE_HIP(hipEventElapsedTime(&clean_ms_[k], clean_ev_[k], clean_ev_[k + 1]));
   therm2_state_ = true;
+}
+
+void ColumnBatch::ridge_times(bool enable, float ms[RIDGE_TIMES]) {
+  ridge_timed_ = enable;
+  for (int k = 0; k < RIDGE_TIMES && ms; ++k) ms[k] = ridge_ms_[k];
 }
 
 void ColumnBatch::cleanup_times(bool enable, float ms[CLEAN_TIMES]) {

@@ -19,6 +19,7 @@
 #include "atmo.h"
 #include "therm.h"
 #include "itd.h"
+#include "ridge.h"
 #include "transport.h"
 #include "batch.h"
 
@@ -107,6 +108,10 @@ struct cice_ctx {
   DevBuf<double> itd_d;
   DevBuf<int32_t> itd_i;
   DevBuf<unsigned long long> itd_rec;
+  // ridging (ridge.h): the namelist values given to cice_ridge_init, the block words of the block-wise entry
+  RidgeParams rp{};
+  bool have_ridge = false;
+  DevBuf<unsigned long long> ridge_w;
   // device is required lazily: domain queries work on a CPU-only host
   // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
   // process may have changed the current device since the last call (another context on another GPU,

@@ -372,6 +372,108 @@ int cice_step_therm2_cleanup(cice_ctx* ctx, double dt, const cice_therm2_cleanup
   CICE_CATCH
 }
 
+int cice_ridge_init(cice_ctx* ctx, int krdg_partic, int krdg_redist, double mu_rdg) {
+  CICE_TRY(ctx)
+  CICE_REQUIRE(krdg_partic == 0 || krdg_partic == 1, "cice_ridge_init: krdg_partic must be 0 or 1");
+  CICE_REQUIRE(krdg_redist == 0 || krdg_redist == 1, "cice_ridge_init: krdg_redist must be 0 or 1");
+  if (krdg_redist == 0)
+    throw Error{CICE_EUNSUPPORTED, "cice_ridge_init: krdg_redist = 0 is not built (the reference indexes hrmax by the "
+                                   "compressed counter of ridging cells; see ridge.h)"};
+  CICE_REQUIRE(mu_rdg > 0.0, "cice_ridge_init: mu_rdg must be positive");
+  c_->rp = RidgeParams{krdg_partic, krdg_redist, mu_rdg};
+  c_->have_ridge = true;
+  CICE_CATCH
+}
+
+// ridge_ice (ice_mechred.F90:133-552) on one block: see include/cice4_amd.h and ridge.h
+int cice_ridge_ice(cice_ctx* ctx, int nx, int ny, double dt, int ntrcr, int icells, const int32_t* indxi,
+                   const int32_t* indxj, const double* rdg_conv, const double* rdg_shear, double* aicen, double* trcrn,
+                   double* vicen, double* vsnon, double* eicen, double* esnon, double* aice0, const int32_t* trcr_depend,
+                   int32_t* l_stop, int32_t* istop, int32_t* jstop, double* dardg1dt, double* dardg2dt, double* dvirdgdt,
+                   double* opening, double* fresh, double* fhocn, int32_t* niter) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(rdg_conv && rdg_shear && aicen && trcrn && vicen && vsnon && eicen && esnon && aice0 && trcr_depend &&
+                   l_stop && istop && jstop, "ridge_ice: NULL argument");
+  CICE_REQUIRE(c_->have_ridge, "cice_ridge_init has not been called");
+  CICE_REQUIRE(dt > 0.0, "ridge_ice: dt");
+  ItdBlock B(c_, nx, ny, icells, indxi, indxj);
+  B.set_tracers(ntrcr, trcr_depend);
+  clear_stop(l_stop, istop, jstop);
+  if (niter) *niter = 0;
+  if (icells == 0) return CICE_OK;     // (the caller's `if (icells > 0)`: nothing is read or written)
+  hipStream_t s = c_->stream;
+  // planes of the staging buffer that the thickness-distribution entries use for other things
+  enum { P_CONV = IB_AINIT, P_SHEAR, P_D1, P_D2, P_DV, P_OPEN, P_WORK = IB_SHIFT };
+  static_assert(P_OPEN < IB_2D && P_WORK + RG_PLANES <= IB_PLANES, "planes of the staging buffer");
+  const ItdState st{aicen, vicen, vsnon, trcrn, eicen, esnon};
+  B.state(st, ST_ALL, true);
+  B.up(IB_2D + I2_AICE0, aice0); B.up(P_CONV, rdg_conv); B.up(P_SHEAR, rdg_shear);
+  const struct { double* h; int plane; } opt[6] = {{dardg1dt, P_D1}, {dardg2dt, P_D2}, {dvirdgdt, P_DV}, {opening, P_OPEN},
+                                                   {fresh, IB_2D + I2_FRESH}, {fhocn, IB_2D + I2_FHOCN}};
+  for (const auto& o : opt)
+    if (o.h) B.up(o.plane, o.h);
+  c_->ridge_w.alloc(RW_WORDS);
+  c_->ridge_w.zero(s);
+  RidgeArgs a{};
+  a.p = B.a.p; a.r = c_->rp;
+  a.nx = nx; a.ny = ny; a.nblocks = 1; a.listpos = B.a.listpos; a.dt = dt;
+  a.rdg_conv = B.pl(P_CONV); a.rdg_shear = B.pl(P_SHEAR);
+  a.aicen = B.a.aicen; a.trcrn = B.a.trcrn; a.vicen = B.a.vicen; a.vsnon = B.a.vsnon; a.eicen = B.a.eicen;
+  a.esnon = B.a.esnon; a.aice0 = B.a.aice0;
+  a.dardg1dt = dardg1dt ? B.pl(P_D1) : nullptr; a.dardg2dt = dardg2dt ? B.pl(P_D2) : nullptr;
+  a.dvirdgdt = dvirdgdt ? B.pl(P_DV) : nullptr; a.opening = opening ? B.pl(P_OPEN) : nullptr;
+  a.fresh = fresh ? B.a.fresh : nullptr; a.fhocn = fhocn ? B.a.fhocn : nullptr;
+  a.work = B.pl(P_WORK); a.bw = c_->ridge_w.p;
+  unsigned long long w[RW_WORDS];
+  for (int done = 0;;) {
+    const int count = std::min<int>(RIDGE_QUEUE, RIDGE_NITERMAX - done);
+    ridge_launch_iterations(a, done + 1, count, s);
+    done += count;
+    CICE_HIP(hipMemcpyAsync(w, a.bw, sizeof w, hipMemcpyDeviceToHost, s));
+    CICE_HIP(hipStreamSynchronize(s));
+    if (!ridge_wants_more(w, done)) break;
+  }
+  unsigned pos = 0;
+  int n_it = 0;
+  const int stop = ridge_decode(w, &pos, &n_it);
+  if (stop == RIDGE_OK) ridge_launch_finish(a, s);
+  B.state(st, ST_ALL, false);
+  B.down(aice0, IB_2D + I2_AICE0);
+  for (const auto& o : opt)
+    if (o.h) B.down(o.h, o.plane);
+  CICE_HIP(hipStreamSynchronize(s));
+  if (niter) *niter = n_it;
+  if (stop != RIDGE_OK) {
+    *l_stop = 1;
+    if (pos) { *istop = indxi[pos - 1]; *jstop = indxj[pos - 1]; }
+  }
+  CICE_CATCH
+}
+
+// The column half of step_dynamics on the batch (ice_step_mod.F90:586-745): see include/cice4_amd.h
+int cice_step_ridge(cice_ctx* ctx, double dt, const cice_ridge_fields* f, int32_t* l_stop, int32_t* istop, int32_t* jstop,
+                    int32_t* bstop, int32_t* stage) {
+  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_REQUIRE(f && l_stop && istop && jstop && bstop && stage, "NULL argument");
+  if (f->ncat == 1) throw Error{CICE_EUNSUPPORTED, "cice_step_ridge: ncat = 1 is not built"};
+  CICE_REQUIRE(f->ncat == NCAT, "cice_step_ridge: ncat is not the library's");
+  NEED_BATCH(true);
+  Halo* halo = nullptr;
+  if (f->bound) {
+    CICE_REQUIRE(c_->have_domain, "cice_step_ridge: bound = 1 needs cice_domain_create");
+    CICE_REQUIRE(c_->batch.same_layout(c_->dom), "cice_step_ridge: the batch does not have the domain's layout");
+    c_->need_halo();
+    halo = c_->halo.get();
+  }
+  c_->batch.step_ridge(c_->itd(), c_->have_ridge ? &c_->rp : nullptr, dt, f, halo, l_stop, istop, jstop, bstop, stage);
+  CICE_CATCH
+}
+
+int cice_ridge_times(cice_ctx* ctx, int enable, float ms[41]) {
+  static_assert(RIDGE_TIMES == 41, "include/cice4_amd.h");
+  CICE_TRY(ctx) c_->batch.ridge_times(enable != 0, ms); CICE_CATCH
+}
+
 int cice_therm2_cleanup_times(cice_ctx* ctx, int enable, float ms[12]) {
   CICE_TRY(ctx) c_->batch.cleanup_times(enable != 0, ms); CICE_CATCH
 }

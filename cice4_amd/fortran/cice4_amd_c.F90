@@ -567,6 +567,49 @@ module cice4_amd_c
       end function
    end interface
 
+   ! mechanical redistribution (source/ice_mechred.F90: ridge_ice; cice4_amd/csrc/ridge.hip) and the column half of
+   ! step_dynamics (source/ice_step_mod.F90:586-745)
+   type, bind(C) :: cice_ridge_fields
+      integer(c_int) :: ncat, bound
+      type(c_ptr) :: aicen, trcrn, vicen, vsnon, eicen, esnon
+      type(c_ptr) :: tmask
+      type(c_ptr) :: rdg_conv, rdg_shear
+      type(c_ptr) :: aice0
+      type(c_ptr) :: dardg1dt, dardg2dt, dvirdgdt, opening
+      type(c_ptr) :: aice, vice, vsno, eice, esno, trcr
+      type(c_ptr) :: fresh, fsalt, fhocn, daidtd, dvidtd
+   end type
+
+   interface
+      integer(c_int) function cice_ridge_init(ctx, krdg_partic, krdg_redist, mu_rdg) bind(C, name='cice_ridge_init')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: krdg_partic, krdg_redist
+         real(c_double), value :: mu_rdg
+      end function
+      ! dardg1dt ... fhocn, niter: c_loc of the array / variable, or c_null_ptr for an absent optional
+      integer(c_int) function cice_ridge_ice(ctx, nx_block, ny_block, dt, ntrcr, icells, indxi, indxj, rdg_conv, rdg_shear, &
+            aicen, trcrn, vicen, vsnon, eicen, esnon, aice0, trcr_depend, l_stop, istop, jstop, dardg1dt, dardg2dt, &
+            dvirdgdt, opening, fresh, fhocn, niter) bind(C, name='cice_ridge_ice')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, ntrcr, icells
+         real(c_double), value :: dt
+         integer(c_int), intent(in) :: indxi(*), indxj(*), trcr_depend(*)
+         real(c_double), intent(in) :: rdg_conv(*), rdg_shear(*)
+         real(c_double), intent(inout) :: aicen(*), trcrn(*), vicen(*), vsnon(*), eicen(*), esnon(*), aice0(*)
+         integer(c_int), intent(out) :: l_stop, istop, jstop
+         type(c_ptr), value :: dardg1dt, dardg2dt, dvirdgdt, opening, fresh, fhocn, niter
+      end function
+      integer(c_int) function cice_step_ridge(ctx, dt, f, l_stop, istop, jstop, bstop, stage) bind(C, name='cice_step_ridge')
+         import
+         type(c_ptr), value :: ctx
+         real(c_double), value :: dt
+         type(cice_ridge_fields), intent(in) :: f
+         integer(c_int), intent(out) :: l_stop, istop, jstop, bstop, stage
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

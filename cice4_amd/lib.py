@@ -113,6 +113,17 @@ class Therm2CleanupFields(C.Structure):
     _fields_ = [("ncat", C.c_int), ("state_resident", C.c_int), ("bound", C.c_int)] + [(n, C.c_void_p) for n in CLEANUP_PTRS]
 
 
+RIDGE_PTRS = ("aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "tmask", "rdg_conv", "rdg_shear", "aice0", "dardg1dt",
+              "dardg2dt", "dvirdgdt", "opening", "aice", "vice", "vsno", "eice", "esno", "trcr", "fresh", "fsalt", "fhocn",
+              "daidtd", "dvidtd")
+RIDGE_NITERMAX = 20
+RIDGE_TIMES = tuple(f"{k}{i}" for i in range(1, RIDGE_NITERMAX + 1) for k in ("rates", "shift")) + ("finish",)
+
+
+class RidgeFields(C.Structure):
+    _fields_ = [("ncat", C.c_int), ("bound", C.c_int)] + [(n, C.c_void_p) for n in RIDGE_PTRS]
+
+
 class ThermoFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in THERMO_STATE + THERMO_FORCING + THERMO_CAT_IN + THERMO_SW
                 + THERMO_OUT + THERMO_ONSET]
@@ -880,6 +891,45 @@ class Context:
         ms = (C.c_float * len(CLEANUP_TIMES))()
         self._ck(self.lib.cice_therm2_cleanup_times(self.h, int(enable), ms))
         return dict(zip(CLEANUP_TIMES, ms))
+
+    # ---- mechanical redistribution (ice_mechred: ridge_ice) ------------------------
+    RIDGE_OPTIONALS = ("dardg1dt", "dardg2dt", "dvirdgdt", "opening", "fresh", "fhocn")
+
+    def ridge_init(self, krdg_partic=1, krdg_redist=1, mu_rdg=4.0):
+        """cice_ridge_init: the namelist's ridging parameters (after itd_init, which gives tracers, tr_lvl, hin_max).
+        krdg_redist = 0 raises CiceError with code CICE_EUNSUPPORTED."""
+        self._ck(self.lib.cice_ridge_init(self.h, int(krdg_partic), int(krdg_redist), C.c_double(mu_rdg)))
+
+    def ridge_ice(self, icells, indxi, indxj, dt, a, optionals=RIDGE_OPTIONALS):
+        """cice_ridge_ice on one block.  a: rdg_conv, rdg_shear, aice0 (ny,nx), aicen, vicen, vsnon (ncat,ny,nx), trcrn
+        (ncat,5,ny,nx), eicen, esnon and the arrays named in `optionals` (the others are absent optionals); updated in
+        place.  Returns (l_stop, istop, jstop, niter)."""
+        ny, nx = a["aice0"].shape
+        ntr, dep = self._itd
+        st = [C.c_int32(0) for _ in range(4)]
+        self._ck(self.lib.cice_ridge_ice(
+            self.h, nx, ny, C.c_double(dt), ntr, icells, _i4(indxi), _i4(indxj),
+            *[_f8(a[k]) for k in ("rdg_conv", "rdg_shear", "aicen", "trcrn", "vicen", "vsnon", "eicen", "esnon", "aice0")],
+            _i4(dep), *[C.byref(x) for x in st[:3]],
+            *[_f8(a[k]) if k in optionals else None for k in self.RIDGE_OPTIONALS], C.byref(st[3])))
+        return tuple(x.value for x in st)
+
+    def step_ridge(self, dt, a, bound=False):
+        """cice_step_ridge on the batch (thermo_batch_alloc).  a: the arrays of RIDGE_PTRS ((nb, ...)).
+        Returns dict(l_stop, istop, jstop, bstop, stage)."""
+        f = RidgeFields()
+        f.ncat, f.bound = NCAT, int(bound)
+        for n in RIDGE_PTRS:
+            setattr(f, n, _i4(a[n]) if n == "tmask" else _f8(a[n]))
+        st = [C.c_int32(0) for _ in range(5)]
+        self._ck(self.lib.cice_step_ridge(self.h, C.c_double(dt), C.byref(f), *[C.byref(x) for x in st]))
+        return dict(zip(("l_stop", "istop", "jstop", "bstop", "stage"), (x.value for x in st)))
+
+    def ridge_times(self, enable=True):
+        """cice_ridge_times: switch the event timing on / off; the times (ms) of the last timed call by RIDGE_TIMES"""
+        ms = (C.c_float * len(RIDGE_TIMES))()
+        self._ck(self.lib.cice_ridge_times(self.h, int(enable), ms))
+        return dict(zip(RIDGE_TIMES, ms))
 
     def therm2_itd_times(self, enable=True):
         """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""

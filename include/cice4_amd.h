@@ -509,7 +509,8 @@ int cice_frzmlt_bottom_lateral(cice_ctx *ctx, int nx_block, int ny_block, int il
 /* ---- thermodynamic changes of the thickness distribution (source/ice_therm_itd.F90): the first half of step_therm2,
  * source/ice_step_mod.F90:286-422 -- rain, aggregate_area, linear_itd, add_new_ice, lateral_melt -- on the device.
  * The second half (:445-511) -- cleanup_itd, bound_state, aggregate, the tendencies -- follows below
- * (cice_step_therm2_cleanup); ridging and shortwave stay with the caller.  No transcendental function on this
+ * (cice_step_therm2_cleanup), and ridging further down (cice_ridge_ice, cice_step_ridge: the column half of
+ * step_dynamics); shortwave stays with the caller.  No transcendental function on this
  * path: results are those of the reference bit for bit (tests/test_gpu_therm_itd.py, tests/golden/therm_itd.npz,
  * tests/test_gpu_cleanup_itd.py, tests/golden/cleanup_itd.npz; the "auscom" flavour compiles the same kernels with its
  * own constants and has no parity fixture yet).
@@ -639,6 +640,56 @@ int cice_step_therm2_cleanup(cice_ctx *ctx, double dt, const cice_therm2_cleanup
 /* Measurement aid (scripts/therm2_cleanup_cost.py), off by default, as cice_therm2_itd_times: the device times (ms) of
  * the last timed cice_step_therm2_cleanup: head, the eight passes of rebin, zap, bound_state, aggregate. */
 int cice_therm2_cleanup_times(cice_ctx *ctx, int enable, float ms[12]);
+
+/* ---- mechanical redistribution (source/ice_mechred.F90: ridge_ice :133-552) on the device ----
+ * cice_ridge_init sets the namelist's ridging parameters; tracer slots, tr_lvl and hin_max are those of cice_itd_init.
+ * krdg_partic 0 (Thorndike et al. 1975) and 1 (exponential) are built.  krdg_redist = 0 is CICE_EUNSUPPORTED: the
+ * reference's ridge_shift indexes hrmax by the compressed counter of ridging cells instead of the cell (:1495-1496,
+ * :1601-1607), so a cell reads another cell's hrmax; reproducing that needs a per-block rank of ridging cells, and no
+ * ice_in of the reference's input_templates uses it. */
+int cice_ridge_init(cice_ctx *ctx, int krdg_partic, int krdg_redist, double mu_rdg);
+/* ridge_ice, one block, host pointers, the reference's argument order; dardg1dt ... fhocn may each be NULL (an absent
+ * optional).  *niter (may be NULL): the iterations the block ran, which the reference prints as "Repeat ridging".
+ * The repeat is block-wide as in the reference: while one listed cell has abs(asum - 1) >= puny every listed cell goes
+ * round again, and the tracers of every cell that is not listed are zeroed (icells = 0: nothing is touched).
+ * Stops, each with the arrays as the reference leaves them:
+ *   aice0 < -puny: the FIRST failing cell in list order; the cells in front of it hold their new aice0, the failing cell
+ *     its negative value, nothing else of that iteration has happened; earlier iterations stay applied; the diagnostics
+ *     and fresh / fhocn are not written;
+ *   ardg > aicen: unreachable in double precision (cice4_amd/csrc/ridge.h); the first category and in it the first cell
+ *     would be named; no fixture, and the state of the other cells is not the reference's then;
+ *   20 iterations without convergence: l_stop with istop = jstop = 0; the state holds 20 iterations; no fixture.
+ * The final "total area > 1" check of the reference is dead behind a loop that exits only when every cell converged. */
+int cice_ridge_ice(cice_ctx *ctx, int nx_block, int ny_block, double dt, int ntrcr, int icells, const int32_t *indxi,
+                   const int32_t *indxj, const double *rdg_conv, const double *rdg_shear, double *aicen, double *trcrn,
+                   double *vicen, double *vsnon, double *eicen, double *esnon, double *aice0,
+                   const int32_t *trcr_depend, int32_t *l_stop, int32_t *istop, int32_t *jstop, double *dardg1dt,
+                   double *dardg2dt, double *dvirdgdt, double *opening, double *fresh, double *fhocn, int32_t *niter);
+/* The column half of step_dynamics (source/ice_step_mod.F90:586-745) as ONE call on the batch, all blocks: stage 1
+ * ridge_ice on the physical tmask cells of every block that has one, 2 cleanup_itd, 3 bound_state, 4 aggregate and
+ * daidtd = (aice - daidtd)/dt, dvidtd = (vice - dvidtd)/dt -- stages 2-4 are stages 1-3 of cice_step_therm2_cleanup, the
+ * same code.  Shapes as there.  The state is uploaded; rdg_conv, rdg_shear and aice0 go in; dardg1dt, dardg2dt, dvirdgdt,
+ * opening go in and out and are written on the listed cells only; fresh, fsalt, fhocn, daidtd, dvidtd go in and out;
+ * aice ... trcr are written.  One download at the end.  bound as in cice_step_therm2_cleanup.
+ * Stops: *stage, *bstop the block (1-based), (istop, jstop) the cell ((0, 0) after 20 iterations).  The failing block
+ * holds what the block-wise entry of that stage leaves, the blocks in front of it have completed the stage, the blocks
+ * behind it come back as they went in; later stages have not run and their outputs are untouched. */
+typedef struct {
+  int ncat, bound;
+  double *aicen, *trcrn, *vicen, *vsnon, *eicen, *esnon;
+  const int32_t *tmask;
+  const double *rdg_conv, *rdg_shear;
+  double *aice0;                                           /* in (ridge_ice) / out (aggregate) */
+  double *dardg1dt, *dardg2dt, *dvirdgdt, *opening;        /* in / out, listed cells */
+  double *aice, *vice, *vsno, *eice, *esno, *trcr;         /* out */
+  double *fresh, *fsalt, *fhocn, *daidtd, *dvidtd;         /* in / out */
+} cice_ridge_fields;
+int cice_step_ridge(cice_ctx *ctx, double dt, const cice_ridge_fields *f, int32_t *l_stop, int32_t *istop,
+                    int32_t *jstop, int32_t *bstop, int32_t *stage);
+/* Measurement aid (scripts/ridge_cost.py), off by default, as cice_therm2_cleanup_times: the device times (ms) of the
+ * last timed cice_step_ridge: ms[2k], ms[2k + 1] the rate kernel and the shift kernel of iteration k + 1 (0 where it was
+ * not queued: a call queues them three at a time while a block asks for more), ms[40] the diagnostics. */
+int cice_ridge_times(cice_ctx *ctx, int enable, float ms[41]);
 
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
