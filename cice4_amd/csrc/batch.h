@@ -10,9 +10,11 @@
 #include "common.h"
 #include "domain.h"
 #include "halo.h"
+#include "handover.h"
 #include "itd.h"
 #include "ridge.h"
 #include "therm.h"
+#include "transport.h"
 
 namespace cice {
 
@@ -100,9 +102,11 @@ class ColumnBatch {
   // halo: the context's ghost-cell update (bound = 1) or nullptr
   void step_therm2_cleanup(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, Halo* halo, int32_t* l_stop,
                            int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
-  void step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f, Halo* halo,
-                  int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
+  // from: the transport whose device buffers hold the state (cice_ridge_chain), or nullptr: the state is uploaded
+  void step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f, Transport* from,
+                  Halo* halo, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
   void ridge_times(bool enable, float ms[RIDGE_TIMES]);
+  void handover_time(bool enable, float* ms);       // the last timed k_state_from_transport (0: none since enabled)
   void set_option(const char* key, int value);      // before or after alloc; kept across re-allocations
   void itd_times(bool enable, float ms[4]);         // likewise
   void cleanup_times(bool enable, float ms[CLEAN_TIMES]);
@@ -130,6 +134,7 @@ class ColumnBatch {
     const RidgeParams* rp;
     const double *rdg_conv, *rdg_shear;
     double *dardg1dt, *dardg2dt, *dvirdgdt, *opening;
+    Transport* from;
   };
   void column_stages(const ItdParams* ip, double dt, const cice_therm2_cleanup_fields* f, const RidgeStage* rs, Halo* halo,
                      int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
@@ -170,6 +175,9 @@ class ColumnBatch {
   hipEvent_t ridge_ev_[2 * RIDGE_QUEUE + 1] = {};
   bool ridge_timed_ = false;
   float ridge_ms_[RIDGE_TIMES] = {};
+  hipEvent_t ho_ev_[2] = {};                 // around k_state_from_transport (handover_time)
+  bool ho_timed_ = false, ho_pending_ = false;
+  float ho_ms_ = 0.0f;
 };
 
 }  // namespace cice

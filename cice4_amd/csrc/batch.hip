@@ -45,6 +45,8 @@ ColumnBatch::~ColumnBatch() {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ridge_ev_)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ho_ev_)
+    if (e) (void)hipEventDestroy(e);
 }
 
 // Every field of cice_thermo_fields, once, in the order the fields travel: what alloc sizes, upload and download move
@@ -473,8 +475,9 @@ void ColumnBatch::step_therm2_cleanup(const ItdParams* ip, double dt, const cice
 }
 
 // The column half of step_dynamics on the batch (ice_step_mod.F90:586-745): ridge_ice in front of the same three stages
-void ColumnBatch::step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f, Halo* halo,
-                             int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage) {
+void ColumnBatch::step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f,
+                             Transport* from, Halo* halo, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop,
+                             int32_t* stage) {
   CICE_REQUIRE(rp, "cice_ridge_init has not been called");
   CICE_REQUIRE(f->rdg_conv && f->rdg_shear && f->dardg1dt && f->dardg2dt && f->dvirdgdt && f->opening,
                "cice_step_ridge: NULL field");
@@ -485,7 +488,7 @@ void ColumnBatch::step_ridge(const ItdParams* ip, const RidgeParams* rp, double 
   c.aice = f->aice; c.aice0 = f->aice0; c.vice = f->vice; c.vsno = f->vsno; c.eice = f->eice; c.esno = f->esno;
   c.trcr = f->trcr;
   c.fresh = f->fresh; c.fsalt = f->fsalt; c.fhocn = f->fhocn; c.daidtt = f->daidtd; c.dvidtt = f->dvidtd;
-  const RidgeStage rs{rp, f->rdg_conv, f->rdg_shear, f->dardg1dt, f->dardg2dt, f->dvirdgdt, f->opening};
+  const RidgeStage rs{rp, f->rdg_conv, f->rdg_shear, f->dardg1dt, f->dardg2dt, f->dvirdgdt, f->opening, from};
   column_stages(ip, dt, &c, &rs, halo, l_stop, istop, jstop, bstop, stage);
 }
 
@@ -515,8 +518,11 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
   for (hipEvent_t& e : clean_ev_)
     if (timed && !e) CICE_HIP(hipEventCreate(&e));
   auto d2 = [&](int k) { return clean_b_.p + (size_t)k * n2; };
+  // the state: resident from step_therm2_itd, handed over by the transport on the device (below), or uploaded
+  Transport* const from = rs ? rs->from : nullptr;
+  const bool late = from && from->download_deferred();   // the host arrays have not seen the transport's result
   fan_->fork(s);
-  if (!resident) {
+  if (!resident && !from) {
     aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
     eicen_.upload(f->eicen, cs()); esnon_.upload(f->esnon, cs());
     for (int it = 0; it < ntr; ++it) tracer_copy(it, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
@@ -534,13 +540,26 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
     ridge_w_.alloc((size_t)nb_ * RW_WORDS);
     const double* in[7] = {rs->rdg_conv, rs->rdg_shear, rs->dardg1dt, rs->dardg2dt, rs->dvirdgdt, rs->opening, f->aice0};
     for (int k = 0; k < 6; ++k) CICE_HIP(hipMemcpyAsync(dr(R_CONV + k), in[k], n2 * 8, hipMemcpyHostToDevice, cs()));
-    CICE_HIP(hipMemcpyAsync(d2(C_AICE0), in[6], n2 * 8, hipMemcpyHostToDevice, cs()));
+    if (!from) CICE_HIP(hipMemcpyAsync(d2(C_AICE0), in[6], n2 * 8, hipMemcpyHostToDevice, cs()));
   }
   fan_->join();
+  if (from) {                          // one launch instead of the uploads of the seven arrays (handover.h)
+    const double* src[HO_ARRAYS];
+    from->state_buffers(src);
+    double* dst[HO_ARRAYS] = {d2(C_AICE0), aicen_.p, vicen_.p, vsnon_.p, eicen_.p, esnon_.p, trcrn_.p};
+    for (hipEvent_t& e : ho_ev_)
+      if (ho_timed_ && !e) CICE_HIP(hipEventCreate(&e));
+    if (ho_timed_) CICE_HIP(hipEventRecord(ho_ev_[0], s));
+    handover_launch(handover_args(nx_, ny_, nb_, ntr, src, dst), s);
+    if (ho_timed_) CICE_HIP(hipEventRecord(ho_ev_[1], s));
+    ho_pending_ = ho_timed_;
+  }
   clear_stop(l_stop, istop, jstop);
   *bstop = 0; *stage = 0;
   const int s0 = rs ? 1 : 0;           // what the stage numbers of the cleanup are shifted by
   // the blocks 0 .. b of the state and of the named planes: what a stop in block b hands back
+  // (late: the blocks behind b "come back as they went in" from the transport's buffers -- everything it holds goes to the
+  // host arrays first, all blocks, aice0 included, and the blocks 0 .. b of this call's result on top of that)
   auto part_state = [&](int b) {
     const size_t m = (size_t)b + 1;
     auto part = [&](double* h, const double* d, size_t per) {
@@ -551,6 +570,11 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
     for (int it = 0; it < ntr; ++it)
       CICE_HIP(hipMemcpy2DAsync(f->trcrn + (size_t)it * np, (size_t)NTRCR * np * 8, trcrn_.p + (size_t)it * np,
                                 (size_t)NTRCR * np * 8, np * 8, (size_t)NCAT * m, hipMemcpyDeviceToHost, cs()));
+  };
+  auto late_state = [&] {
+    if (!late) return;
+    const cice_transport_fields t{f->aice0, f->aicen, f->trcrn, f->vicen, f->vsnon, f->eicen, f->esnon, nullptr, nullptr};
+    from->download_state(t);
   };
   if (rs) {
     CICE_HIP(hipMemsetAsync(ridge_w_.p, 0, ridge_w_.n * 8, s));
@@ -596,6 +620,7 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
       *l_stop = 1; *stage = 1; *bstop = b + 1;
       if (pos) { *istop = (int32_t)((pos - 1) % nx_) + 1; *jstop = (int32_t)((pos - 1) / nx_) + 1; }
       const size_t m = (size_t)b + 1;
+      late_state();
       fan_->fork(s);
       part_state(b);
       double* h[7] = {rs->dardg1dt, rs->dardg2dt, rs->dvirdgdt, rs->opening, f->aice0, f->fresh, f->fhocn};
@@ -627,6 +652,7 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
     *l_stop = 1; *stage = 1 + s0; *bstop = b + 1;
     *istop = (int32_t)(q % nx_) + 1; *jstop = (int32_t)(q / nx_) + 1;
     const size_t m = (size_t)b + 1;
+    late_state();
     fan_->fork(s);
     part_state(b);
     double* h[3] = {f->fresh, f->fsalt, f->fhocn};
@@ -680,6 +706,16 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
   CICE_HIP(hipStreamSynchronize(s));
   for (int k = 0; k < CLEAN_TIMES && timed; ++k) CICE_HIP(hipEventElapsedTime(&clean_ms_[k], clean_ev_[k], clean_ev_[k + 1]));
   therm2_state_ = true;
+}
+
+void ColumnBatch::handover_time(bool enable, float* ms) {
+  if (ho_pending_) {                   // (every path of column_stages has waited for the stream since)
+    CICE_HIP(hipEventElapsedTime(&ho_ms_, ho_ev_[0], ho_ev_[1]));
+    ho_pending_ = false;
+  }
+  if (ms) *ms = ho_ms_;
+  if (enable != ho_timed_) ho_ms_ = 0.0f;
+  ho_timed_ = enable;
 }
 
 void ColumnBatch::ridge_times(bool enable, float ms[RIDGE_TIMES]) {

@@ -67,6 +67,18 @@ struct cice_ctx {
   cice_transport_fields chain{};
   bool chain_on = false, chain_ready = false;
   const double *chain_aicen = nullptr, *chain_vicen = nullptr, *chain_u = nullptr, *chain_v = nullptr;   // what cice_evp was given
+  // transport -> ridging hand-over (cice_ridge_chain).  ridge_armed: the last entry was a cice_transport_remap that ended
+  // without a stop, its result is in the transport's device buffers and ridge_f names the host arrays it was given;
+  // Transport::download_deferred(): ... and those arrays have not received it (mode 2).  Every entry but the consuming
+  // cice_step_ridge ends this in its frame (end_handover): a deferred download is made good first.
+  int ridge_mode = 0;
+  bool ridge_armed = false;
+  cice_transport_fields ridge_f{};
+  void end_handover() {
+    if (!ridge_armed) return;
+    ridge_armed = false;       // (first: a flush that throws must not be tried again with arrays that may be gone)
+    if (transport && transport->download_deferred()) transport->download_state(ridge_f);
+  }
   double chio = 0.006;         // coupled flavour: the namelist's chio (cice_thermo_set_chio)
   double nml[4] = {1.0, 0.0, 0.00536, 0.0};   // coupled flavour: cosw, sinw, dragio, use_ocnslope last sent to the device
   bool nml_set = false;
@@ -124,18 +136,26 @@ struct cice_ctx {
   void connect(Halo& h);       // hands this rank's communicator or link, if any, to a Halo built on the domain
 };
 
-#define CICE_TRY_QUEUED(ctx_) \
+#define CICE_TRY_BARE(ctx_) \
   cice_ctx* c_ = (ctx_); \
   if (!c_) return CICE_EINVAL; \
   try {                        \
     c_->bind_device();         \
     c_->fan.forked = false;   /* an entry that failed between fork and join leaves nothing behind for the next */
+// Every entry but the consumer of the transport -> ridging hand-over (cice_step_ridge, which reads ridge_armed first and ends
+// the hand-over itself) ends it here: a state whose download was deferred reaches the host arrays before the entry runs.
+#define CICE_TRY_QUEUED(ctx_) \
+  CICE_TRY_BARE(ctx_)         \
+    c_->end_handover();
 // Every entry but the two that may leave one-launch EVP loops pending (cice_evp_subcycles, and cice_evp_get_info asked for
 // "resident_pending") first looks at the records of the pending ones (Evp::retire_resident): whatever it reads, launches or
 // changes then finds the state a wait behind every loop would have left.
-#define CICE_TRY(ctx_)  \
-  CICE_TRY_QUEUED(ctx_) \
+#define CICE_TRY_HANDOVER(ctx_) \
+  CICE_TRY_BARE(ctx_)           \
     if (c_->evp) c_->evp->retire_resident();
+#define CICE_TRY(ctx_)      \
+  CICE_TRY_HANDOVER(ctx_)   \
+    c_->end_handover();
 #define CICE_CATCH                                            \
   }                                                           \
   catch (const Error& e) {                                    \

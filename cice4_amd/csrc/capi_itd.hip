@@ -453,7 +453,14 @@ int cice_ridge_ice(cice_ctx* ctx, int nx, int ny, double dt, int ntrcr, int icel
 // The column half of step_dynamics on the batch (ice_step_mod.F90:586-745): see include/cice4_amd.h
 int cice_step_ridge(cice_ctx* ctx, double dt, const cice_ridge_fields* f, int32_t* l_stop, int32_t* istop, int32_t* jstop,
                     int32_t* bstop, int32_t* stage) {
-  CICE_TRY(ctx) c_->chain_ready = false;
+  CICE_TRY_HANDOVER(ctx) c_->chain_ready = false;
+  // the consumer of the transport -> ridging hand-over: given the arrays the armed transport call was given, it takes the
+  // state from the transport's device buffers; anything else ends the hand-over as every other entry does
+  const cice_transport_fields& t = c_->ridge_f;
+  const bool handed = c_->ridge_armed && f && f->aice0 == t.aice0 && f->aicen == t.aicen && f->trcrn == t.trcrn &&
+                      f->vicen == t.vicen && f->vsnon == t.vsnon && f->eicen == t.eicen && f->esnon == t.esnon;
+  if (!handed) c_->end_handover();
+  // (handed: from here on a throw leaves the hand-over armed, and the next entry's frame makes a deferred download good)
   CICE_REQUIRE(f && l_stop && istop && jstop && bstop && stage, "NULL argument");
   if (f->ncat == 1) throw Error{CICE_EUNSUPPORTED, "cice_step_ridge: ncat = 1 is not built"};
   CICE_REQUIRE(f->ncat == NCAT, "cice_step_ridge: ncat is not the library's");
@@ -465,13 +472,22 @@ int cice_step_ridge(cice_ctx* ctx, double dt, const cice_ridge_fields* f, int32_
     c_->need_halo();
     halo = c_->halo.get();
   }
-  c_->batch.step_ridge(c_->itd(), c_->have_ridge ? &c_->rp : nullptr, dt, f, halo, l_stop, istop, jstop, bstop, stage);
+  c_->batch.step_ridge(c_->itd(), c_->have_ridge ? &c_->rp : nullptr, dt, f, handed ? c_->transport.get() : nullptr, halo,
+                       l_stop, istop, jstop, bstop, stage);
+  if (handed) {                        // consumed: the host arrays hold what this call downloaded
+    c_->ridge_armed = false;
+    c_->transport->forget_state();
+  }
   CICE_CATCH
 }
 
 int cice_ridge_times(cice_ctx* ctx, int enable, float ms[41]) {
   static_assert(RIDGE_TIMES == 41, "include/cice4_amd.h");
   CICE_TRY(ctx) c_->batch.ridge_times(enable != 0, ms); CICE_CATCH
+}
+
+int cice_ridge_chain_time(cice_ctx* ctx, int enable, float* ms) {
+  CICE_TRY(ctx) c_->batch.handover_time(enable != 0, ms); CICE_CATCH
 }
 
 int cice_therm2_cleanup_times(cice_ctx* ctx, int enable, float ms[12]) {

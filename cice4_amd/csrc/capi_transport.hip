@@ -23,7 +23,29 @@ int cice_transport_remap(cice_ctx* ctx, double dt, const cice_transport_fields* 
       f->aicen == c_->chain_aicen && f->vicen == c_->chain_vicen && f->uvel == c_->chain_u && f->vvel == c_->chain_v)
     c_->transport->adopt(c_->evp->d_uv(), c_->evp->d_aicen(), c_->evp->d_vicen());
   c_->chain_ready = false;
-  c_->transport->remap(dt, *f, l_stop, istop, jstop);
+  // transport -> ridging hand-over: what cice_step_ridge will need to take this call's result from the device
+  const bool can_arm = c_->ridge_mode != 0 && c_->have_itd && c_->have_ridge && c_->batch.allocated() &&
+                       c_->batch.same_layout(c_->dom) && c_->transport->same_tracers(c_->ip.ntrcr, c_->ip.dep);
+  c_->transport->defer_download = can_arm && c_->ridge_mode == 2;
+  int32_t stop = 0;
+  c_->transport->remap(dt, *f, &stop, istop, jstop);
+  if (l_stop) *l_stop = stop;
+  if (can_arm && stop == 0 && c_->transport->state_ready()) {
+    c_->ridge_f = *f;
+    c_->ridge_armed = true;
+  }
+  CICE_CATCH
+}
+
+int cice_ridge_chain(cice_ctx* ctx, int mode) {
+  CICE_TRY(ctx)
+  CICE_REQUIRE(mode >= 0 && mode <= 2, "cice_ridge_chain: mode must be 0, 1 or 2");
+  c_->ridge_mode = mode;
+  CICE_CATCH
+}
+
+int cice_transport_download_state(cice_ctx* ctx) {
+  CICE_TRY(ctx)   // (the frame has done it)
   CICE_CATCH
 }
 

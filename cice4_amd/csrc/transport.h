@@ -39,6 +39,18 @@ class Transport {
   void prefetch(const cice_transport_fields& f);
   void adopt(const double* d_uv, const double* d_aicen, const double* d_vicen);
   bool chained = false;   // the state of the next remap() is on the device already
+  // transport -> ridging hand-over (cice_ridge_chain, handover.h).  defer_download: the next remap() leaves its result on
+  // the device if it ends without a stop (read and reset like `chained`); state_ready(): the last remap() ran through and
+  // the seven device buffers hold its result; download_deferred(): ... and the host arrays have not received it.
+  bool defer_download = false;
+  bool state_ready() const { return ready; }
+  bool download_deferred() const { return deferred; }
+  void forget_state() { ready = deferred = false; }
+  // the result of the last remap() into host arrays, all blocks (what remap() does itself unless it deferred)
+  void download_state(const cice_transport_fields& f);
+  // the seven state buffers, (nx, ny, nblocks) per level, in handover.h's order
+  void state_buffers(const double* out[7]) const;
+  bool same_tracers(int ntrcr_, const int* depend_) const;
   // test aid: stop the next remap() after kernel stage `s` (1 tracers, 2 fields + departure points + their halos,
   // 3 fluxes, 4 update; 0 = run through) and copy a work array to the host (0 mm, 1 tm, 2 mc|tc, 3 mx|tx|my|ty,
   // 4 dpx|dpy, 5 mflx, 6 mtflx, 7 mmask, 8 tmask); returns the number of doubles
@@ -53,6 +65,9 @@ class Transport {
   CopyFan& fan;  // the context's side streams for the state upload / download
   size_t n = 0;  // nblocks * nx_block * ny_block
   int ntrace = 0, ntrcr = 0;
+  int depend[NTRCR] = {};
+  bool ready = false, deferred = false;
+  void queue_download(const cice_transport_fields& f);
   void up(double* d, const double* h, int levels);   // host (nx,ny,levels,nblocks) -> device (nx,ny,nblocks) per level
   TransportKernelArgs a{};
   DevBuf<int32_t> blk;

@@ -614,6 +614,7 @@ void Transport::init(const cice_transport_config& c, const cice_transport_grid& 
     const int d = c.trcr_depend[it];
     CICE_REQUIRE(d >= 0 && d <= 2, "cice_transport_init: trcr_depend must be 0, 1 or 2");
     if (d) { a.type[2 + it] = 2; a.dep[2 + it] = d - 1; }
+    depend[it] = d;
   }
   for (int l = 0; l < NILYR; ++l) { a.type[2 + ntrcr + l] = 2; a.dep[2 + ntrcr + l] = 0; }
   for (int l = 0; l < NSLYR; ++l) { a.type[2 + ntrcr + NILYR + l] = 2; a.dep[2 + ntrcr + NILYR + l] = 1; }
@@ -686,20 +687,14 @@ void Transport::adopt(const double* d_uv, const double* d_aicen, const double* d
 void Transport::remap(double dt, const cice_transport_fields& f, int32_t* l_stop, int32_t* istop, int32_t* jstop) {
   const bool was_chained = chained;   // (read and reset before anything can throw: a failed call must not leave the NEXT one chained)
   chained = false;
+  const bool defer = defer_download;  // (likewise)
+  defer_download = false;
+  ready = deferred = false;
   CICE_REQUIRE(n > 0, "cice_transport_init has not been called");
   CICE_REQUIRE(f.aice0 && f.aicen && f.trcrn && f.vicen && f.vsnon && f.eicen && f.esnon && f.uvel && f.vvel,
                "cice_transport_remap: NULL field");
   const size_t np = (size_t)dom.nx_block * dom.ny_block;
   const int nb = dom.nblocks();
-  auto down = [&](double* h, const double* d, int levels) {
-    if (levels == 1 || nb == 1) {
-      CICE_HIP(hipMemcpyAsync(h, d, (size_t)levels * n * 8, hipMemcpyDeviceToHost, fan.next()));
-      return;
-    }
-    for (int b = 0; b < nb; ++b)
-      CICE_HIP(hipMemcpy2DAsync(h + (size_t)b * levels * np, np * 8, d + (size_t)b * np, n * 8, np * 8, levels,
-                                hipMemcpyDeviceToHost, fan.next()));
-  };
   fan.fork(stream);
   if (!was_chained) {   // (chained: five arrays were prefetched during evp, four came from the dynamics' device buffers)
     up(aice0.p, f.aice0, 1); up(aicen.p, f.aicen, NCAT); up(trcrn.p, f.trcrn, NCAT * NTRCR); up(vicen.p, f.vicen, NCAT);
@@ -741,14 +736,18 @@ void Transport::remap(double dt, const cice_transport_fields& f, int32_t* l_stop
   halo.update_r8(eicen.p, NCAT * NILYR, n, true, LOC_CENTER, KIND_SCALAR);
   halo.update_r8(esnon.p, NCAT * NSLYR, n, true, LOC_CENTER, KIND_SCALAR);
   CICE_HIP(hipGetLastError());
-  fan.fork(stream);
-  down(f.aice0, aice0.p, 1); down(f.aicen, aicen.p, NCAT); down(f.trcrn, trcrn.p, NCAT * NTRCR);
-  down(f.vicen, vicen.p, NCAT); down(f.vsnon, vsnon.p, NCAT); down(f.eicen, eicen.p, NCAT * NILYR);
-  down(f.esnon, esnon.p, NCAT * NSLYR);
-  fan.join();
   unsigned long long hk = 0;
-  CICE_HIP(hipMemcpyAsync(&hk, key.p, 8, hipMemcpyDeviceToHost, stream));
-  CICE_HIP(hipStreamSynchronize(stream));
+  if (defer) {   // the download only if the call stops: the key first
+    CICE_HIP(hipMemcpyAsync(&hk, key.p, 8, hipMemcpyDeviceToHost, stream));
+    CICE_HIP(hipStreamSynchronize(stream));
+    deferred = hk == ~0ull;
+  }
+  if (!deferred) {
+    queue_download(f);
+    CICE_HIP(hipMemcpyAsync(&hk, key.p, 8, hipMemcpyDeviceToHost, stream));
+    CICE_HIP(hipStreamSynchronize(stream));
+  }
+  ready = hk == ~0ull;   // (the state arrays of a failed call are not defined)
   if (l_stop) *l_stop = 0;
   if (istop) *istop = 0;
   if (jstop) *jstop = 0;
@@ -758,6 +757,46 @@ void Transport::remap(double dt, const cice_transport_fields& f, int32_t* l_stop
     if (jstop) *jstop = (int32_t)(q / dom.nx_block) + 1;
     if (istop) *istop = (int32_t)(q % dom.nx_block) + 1;
   }
+}
+
+// device (nx,ny,nblocks) per level -> host (nx,ny,levels,nblocks), every array of the state, on the copy streams
+void Transport::queue_download(const cice_transport_fields& f) {
+  const size_t np = (size_t)dom.nx_block * dom.ny_block;
+  const int nb = dom.nblocks();
+  auto down = [&](double* h, const double* d, int levels) {
+    if (levels == 1 || nb == 1) {
+      CICE_HIP(hipMemcpyAsync(h, d, (size_t)levels * n * 8, hipMemcpyDeviceToHost, fan.next()));
+      return;
+    }
+    for (int b = 0; b < nb; ++b)
+      CICE_HIP(hipMemcpy2DAsync(h + (size_t)b * levels * np, np * 8, d + (size_t)b * np, n * 8, np * 8, levels,
+                                hipMemcpyDeviceToHost, fan.next()));
+  };
+  fan.fork(stream);
+  down(f.aice0, aice0.p, 1); down(f.aicen, aicen.p, NCAT); down(f.trcrn, trcrn.p, NCAT * NTRCR);
+  down(f.vicen, vicen.p, NCAT); down(f.vsnon, vsnon.p, NCAT); down(f.eicen, eicen.p, NCAT * NILYR);
+  down(f.esnon, esnon.p, NCAT * NSLYR);
+  fan.join();
+}
+
+void Transport::download_state(const cice_transport_fields& f) {
+  CICE_REQUIRE(ready, "Transport::download_state: no result on the device");
+  CICE_REQUIRE(f.aice0 && f.aicen && f.trcrn && f.vicen && f.vsnon && f.eicen && f.esnon, "Transport::download_state: NULL field");
+  queue_download(f);
+  CICE_HIP(hipStreamSynchronize(stream));
+  deferred = false;
+}
+
+void Transport::state_buffers(const double* out[7]) const {
+  const double* b[7] = {aice0.p, aicen.p, vicen.p, vsnon.p, eicen.p, esnon.p, trcrn.p};
+  for (int k = 0; k < 7; ++k) out[k] = b[k];
+}
+
+bool Transport::same_tracers(int ntrcr_, const int* depend_) const {
+  if (ntrcr_ != ntrcr) return false;
+  for (int it = 0; it < ntrcr; ++it)
+    if (depend_[it] != depend[it]) return false;
+  return true;
 }
 
 size_t Transport::debug_fetch(int which, double* out) {

@@ -608,6 +608,16 @@ module cice4_amd_c
          type(cice_ridge_fields), intent(in) :: f
          integer(c_int), intent(out) :: l_stop, istop, jstop, bstop, stage
       end function
+      ! transport -> ridging hand-over on the device: mode 0 off, 1 download kept, 2 download deferred
+      integer(c_int) function cice_ridge_chain(ctx, mode) bind(C, name='cice_ridge_chain')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: mode
+      end function
+      integer(c_int) function cice_transport_download_state(ctx) bind(C, name='cice_transport_download_state')
+         import
+         type(c_ptr), value :: ctx
+      end function
    end interface
 
    ! one context per MPI task (= per GPU), shared by the drop-in modules

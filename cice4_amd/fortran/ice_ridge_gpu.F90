@@ -9,6 +9,13 @@
 ! krdg_redist = 0 is refused by the library (CICE_EUNSUPPORTED; cice4_amd/csrc/ridge.h says why).
 ! The library addresses trcrn as (nx_block,ny_block,max_ntrcr,ncat); the callers hand in the section
 ! trcrn(:,:,1:ntrcr,:,iblk), which is copied into an array of that shape and back.
+!
+! step_ridge_gpu is the one-call form: everything step_dynamics does behind transport_remap (ridge_ice on every block,
+! cleanup_itd, bound_state, aggregate, the tendencies; source/ice_step_mod.F90:586-745) as ONE cice_step_ridge on the
+! module arrays of ice_state, ice_flux and ice_grid.  It is what a driver needs that keeps the state on the device from
+! the transport into ridging (cice_ridge_chain; CICE4_AMD_CHAIN_RIDGE of ice_transport_driver): the seven state arrays
+! it names are the ones transport_remap names.  Its first call makes the init calls and allocates the batch, so the
+! hand-over starts with the second step.
 !=======================================================================
       module ice_ridge_gpu
 
@@ -22,9 +29,10 @@
       implicit none
       save
       private
-      public :: ridge_ice
+      public :: ridge_ice, step_ridge_gpu
 
-      logical, private :: ridge_ready = .false.
+      logical, private :: ridge_ready = .false., batch_ready = .false.
+      integer (c_int), allocatable, target, private :: tmask_i4(:,:,:)
 
       contains
 
@@ -113,5 +121,48 @@
       if (niter > 1) write(nu_diag,*) 'Repeat ridging (GPU), niter =', niter - 1
       if (l_stop) write(nu_diag,*) 'Ridging error (GPU) at i, j =', istop, jstop, ' after niter =', niter
       end subroutine ridge_ice
+
+!=======================================================================
+! stage (0 without a stop): 1 ridge_ice, 2 cleanup_itd; bstop the local block, (istop, jstop) the cell in it -- the
+! caller prints them and aborts as step_dynamics does (ice_step_mod.F90:640-649, 683-692)
+      subroutine step_ridge_gpu (dt, l_stop, istop, jstop, bstop, stage)
+      use ice_blocks, only: nx_block, ny_block
+      use ice_domain, only: nblocks
+      use ice_grid, only: tmask
+      use ice_state, only: aicen, trcrn, vicen, vsnon, eicen, esnon, aice0, aice, vice, vsno, eice, esno, trcr
+      use ice_flux, only: rdg_conv, rdg_shear, dardg1dt, dardg2dt, dvirdgdt, opening, fresh, fsalt, fhocn, &
+                          daidtd, dvidtd
+      use ice_itd, only: hin_max
+      real (kind=dbl_kind), intent(in) :: dt
+      logical (kind=log_kind), intent(out) :: l_stop
+      integer (kind=int_kind), intent(out) :: istop, jstop, bstop, stage
+      type (cice_ridge_fields) :: f
+      integer (c_int) :: ls
+
+      call ridge_ensure
+      if (.not. batch_ready) then
+         call cice_gpu_check(cice_thermo_batch_alloc(cice_gpu_ctx, nx_block, ny_block, nblocks), 'step_ridge_gpu')
+         allocate (tmask_i4(nx_block,ny_block,nblocks))
+         batch_ready = .true.
+      endif
+      hin_max(ncat) = 1.0e+8_dbl_kind    ! the reference's side effect (ridge_prep, ice_mechred.F90:695)
+      tmask_i4 = merge(1, 0, tmask(:,:,1:nblocks))
+      f%ncat = ncat
+      f%bound = 1
+      f%aicen = addr_r8(aicen); f%trcrn = addr_r8(trcrn); f%vicen = addr_r8(vicen); f%vsnon = addr_r8(vsnon)
+      f%eicen = addr_r8(eicen); f%esnon = addr_r8(esnon)
+      f%tmask = c_loc(tmask_i4)
+      f%rdg_conv = addr_r8(rdg_conv); f%rdg_shear = addr_r8(rdg_shear)
+      f%aice0 = addr_r8(aice0)
+      f%dardg1dt = addr_r8(dardg1dt); f%dardg2dt = addr_r8(dardg2dt); f%dvirdgdt = addr_r8(dvirdgdt)
+      f%opening = addr_r8(opening)
+      f%aice = addr_r8(aice); f%vice = addr_r8(vice); f%vsno = addr_r8(vsno); f%eice = addr_r8(eice)
+      f%esno = addr_r8(esno); f%trcr = addr_r8(trcr)
+      f%fresh = addr_r8(fresh); f%fsalt = addr_r8(fsalt); f%fhocn = addr_r8(fhocn)
+      f%daidtd = addr_r8(daidtd); f%dvidtd = addr_r8(dvidtd)
+      call cice_gpu_check(cice_step_ridge(cice_gpu_ctx, dt, f, ls, istop, jstop, bstop, stage), 'step_ridge_gpu')
+      l_stop = (ls /= 0)
+      if (l_stop) write(nu_diag,*) 'step_ridge_gpu: stop in stage', stage, ' block', bstop, ' at i, j =', istop, jstop
+      end subroutine step_ridge_gpu
 
       end module ice_ridge_gpu

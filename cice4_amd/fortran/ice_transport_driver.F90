@@ -91,6 +91,18 @@
             if (my_task == master_task) write(nu_diag,*) &
                'transport_remap takes its state from the device after evp (CICE4_AMD_CHAIN=1)'
          endif
+         ! transport -> ridging without the upload (include/cice4_amd.h: cice_ridge_chain): a driver whose step_dynamics
+         ! goes on with ONE cice_step_ridge call on these module arrays (ice_ridge_gpu: step_ridge_gpu) and writes nothing
+         ! to them in between.  CICE4_AMD_CHAIN_RIDGE=1: the download here is kept; =2: it is left to step_ridge_gpu (any
+         ! other call into the library makes it good first).  Harmless with a driver that ridges block by block: the
+         ! block-wise cice_ridge_ice ends the hand-over like every other entry.
+         chain_env = ' '
+         call get_environment_variable('CICE4_AMD_CHAIN_RIDGE', chain_env)
+         if (trim(chain_env) == '1' .or. trim(chain_env) == '2') then
+            call cice_gpu_check(cice_ridge_chain(cice_gpu_ctx, merge(1, 2, trim(chain_env) == '1')), 'cice_ridge_chain')
+            if (my_task == master_task) write(nu_diag,*) &
+               'transport_remap hands its state to step_ridge on the device (CICE4_AMD_CHAIN_RIDGE=', trim(chain_env), ')'
+         endif
       endif
       call cice_gpu_check(cice_transport_remap(cice_gpu_ctx, dt, f, l_stop, istop, jstop), 'transport_remap')
       if (l_stop /= 0) then

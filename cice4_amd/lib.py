@@ -694,8 +694,31 @@ class Context:
         for n, _t in TransportFields._fields_:
             setattr(f, n, _f8(s[n]))
         st = [C.c_int32(0) for _ in range(3)]
+        if getattr(self, "_ridge_mode", 0) == 2:
+            self._handover = s   # keep the arrays alive: a deferred download lands in them (ridge_chain)
         self._ck(self.lib.cice_transport_remap(self.h, C.c_double(dt), C.byref(f), *[C.byref(x) for x in st]))
         return tuple(x.value for x in st)
+
+    def ridge_chain(self, mode):
+        """cice_ridge_chain: 0 off; 1: a step_ridge that follows a transport_remap and is given the SAME seven state
+        arrays (aice0, aicen, trcrn, vicen, vsnon, eicen, esnon) takes the state from the transport's device buffers
+        instead of uploading it; 2: as 1, and such a transport_remap leaves its result on the device -- the host arrays
+        receive the state from step_ridge, from any other call on this context, or from transport_download_state()."""
+        self._ck(self.lib.cice_ridge_chain(self.h, int(mode)))
+        self._ridge_mode = int(mode)
+        self._handover = None
+
+    def ridge_chain_time(self, enable=True):
+        """cice_ridge_chain_time: switch the event timing of the hand-over kernel on / off; the time (ms) of the last
+        timed one"""
+        ms = C.c_float(0.0)
+        self._ck(self.lib.cice_ridge_chain_time(self.h, int(enable), C.byref(ms)))
+        return ms.value
+
+    def transport_download_state(self):
+        """cice_transport_download_state: a transport result whose download was deferred (ridge_chain(2)) goes to the
+        arrays that transport_remap call was given, and the hand-over ends; nothing happens if none is pending."""
+        self._ck(self.lib.cice_transport_download_state(self.h))
 
     def transport_chain(self, s):
         """cice_transport_chain: s = the arrays the following transport_remap calls will be given (None ends the chain).

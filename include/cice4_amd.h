@@ -768,6 +768,36 @@ int cice_debug_balance_strip(int rows, int n, const int32_t *ends, const double 
  * sets it up on its FIRST transport_remap call (the first step's evp is therefore unchained) when CICE4_AMD_CHAIN=1 is in
  * the environment. */
 int cice_transport_chain(cice_ctx *ctx, const cice_transport_fields *fields);
+/* transport -> ridging WITHOUT the upload.  In step_dynamics `call transport_remap(dt)` is followed by ridge_ice, cleanup_itd,
+ * bound_state and aggregate (source/ice_step_mod.F90:600-745) and nothing else touches the state in between: what
+ * cice_transport_remap downloads, cice_step_ridge uploads again a moment later.  cice_ridge_chain(ctx, mode) hands the state
+ * over on the device; mode 0 (the default) is off, other values are CICE_EINVAL.
+ *   mode 1: cice_transport_remap behaves as always, download included, and ARMS the hand-over if it returned CICE_OK with
+ *     l_stop = 0, cice_itd_init and cice_ridge_init have been called, the batch (cice_thermo_batch_alloc) has the domain's
+ *     layout and the transport's ntrcr and trcr_depend are those of cice_itd_init.  A cice_step_ridge that is then given the
+ *     same seven state arrays (aice0, aicen, trcrn, vicen, vsnon, eicen, esnon: the same pointers) uploads none of them: one
+ *     kernel fills the batch from the transport's device buffers.  Everything else travels as always.  The host arrays hold a
+ *     valid state at every moment.  CONTRACT (the caller's statement): nothing writes to the seven arrays between the two
+ *     calls -- the device copy is what ridging reads.
+ *   mode 2: as mode 1, and a transport call that arms the hand-over SKIPS its download (only then: if a condition fails it
+ *     downloads as always and does not arm; a call that stops downloads).  Until the consuming cice_step_ridge returns, the
+ *     seven host arrays hold what went into the transport call.  The consumer downloads the final state as always; after a
+ *     stop in it ALL blocks of the state and of aice0 reach the host (the blocks behind the failing one as the transport left
+ *     them), so that the host arrays are what they are with mode 0.
+ * Only the matching cice_step_ridge consumes the hand-over.  EVERY other entry that is given this context (cice_last_error
+ * and the cice_domain_* queries, which only read the block tables, aside) -- the cice_evp*,
+ * cice_thermo_*, cice_step_therm*, cice_transport_* and halo entries, a cice_step_ridge with other pointers (which uploads as
+ * always), cice_ridge_chain itself -- first copies a deferred state into the arrays the transport call was given and then
+ * disarms: the library never loses a deferred state, and a caller who needs it on the host in between asks for it with
+ * cice_transport_download_state (CICE_OK whether or not something was pending).  The one exception is cice_destroy, which
+ * drops a pending state WITHOUT copying: the host arrays may be gone by then.  The evp -> transport chain above is
+ * independent of this one; both can be on.  The Fortran drop-in switches it on at its first transport_remap call when
+ * CICE4_AMD_CHAIN_RIDGE=1 or =2 is in the environment. */
+int cice_ridge_chain(cice_ctx *ctx, int mode);
+int cice_transport_download_state(cice_ctx *ctx);
+/* Measurement aid (scripts/ridge_chain_cost.py), off by default, as cice_ridge_times: *ms (may be NULL) = the device time
+ * (ms) of the hand-over kernel of the last timed cice_step_ridge that consumed a hand-over, 0 if there was none. */
+int cice_ridge_chain_time(cice_ctx *ctx, int enable, float *ms);
 /* advection = 'upwind' (source/ice_transport_driver.F90:672-834 transport_upwind with state_to_work :1570, upwind_field
  * :1796, work_to_state :1686 and compute_tracers, source/ice_itd.F90:1482): first-order donor-cell transport of aice0, of
  * every category's area, volumes and tracers and of the layer enthalpies, then bound_state, on the device.  HTE, HTN,
