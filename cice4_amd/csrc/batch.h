@@ -13,6 +13,7 @@
 #include "handover.h"
 #include "itd.h"
 #include "ridge.h"
+#include "shortwave.h"
 #include "therm.h"
 #include "transport.h"
 
@@ -106,6 +107,11 @@ class ColumnBatch {
   void step_ridge(const ItdParams* ip, const RidgeParams* rp, double dt, const cice_ridge_fields* f, Transport* from,
                   Halo* halo, int32_t* l_stop, int32_t* istop, int32_t* jstop, int32_t* bstop, int32_t* stage);
   void ridge_times(bool enable, float ms[RIDGE_TIMES]);
+  // step_radiation / prep_radiation for shortwave = 'default' (shortwave.h); sp: the parameters of cice_shortwave_init
+  void step_radiation(const ThermoParams* tp, const ShortwaveParams* sp, const cice_radiation_fields* f);
+  void prep_radiation(const ThermoParams* tp, const cice_prep_radiation_fields* f);
+  void radiation_chain(int mode);                   // cice_radiation_chain
+  void radiation_times(bool enable, float ms[2]);   // the last timed k_shortwave_ccsm3, k_prep_radiation
   void handover_time(bool enable, float* ms);       // the last timed k_state_from_transport (0: none since enabled)
   void set_option(const char* key, int value);      // before or after alloc; kept across re-allocations
   void itd_times(bool enable, float ms[4]);         // likewise
@@ -122,7 +128,9 @@ class ColumnBatch {
   std::vector<Field> fields(const cice_thermo_fields* h);
   hipStream_t cs() { return fan_->forked ? fan_->next() : stream_; }   // the stream for the next host <-> device copy
   void tracer_copy(int it, const double* from, double* to, hipMemcpyKind kind);
-  void upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef);
+  // with_sw = false: the five shortwave arrays stay behind (cice_radiation_chain: the device copies are the host's)
+  void upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef,
+                     bool with_sw = true);
   void download_fields(const ThermoParams* tp, cice_thermo_fields* h);
   void launch_step(const ThermoParams& tp, double dt, double yday, unsigned long long status[THERMO_STATUS_WORDS],
                    float* elapsed_ms, hipEvent_t* ev);
@@ -175,6 +183,19 @@ class ColumnBatch {
   hipEvent_t ridge_ev_[2 * RIDGE_QUEUE + 1] = {};
   bool ridge_timed_ = false;
   float ridge_ms_[RIDGE_TIMES] = {};
+  // radiation stage: its 2-d fields, the six albedo outputs, prep_radiation's copy of aicen.  sw_resident_: fswsfc_,
+  // fswint_, fswthrun_, Sswabs_, Iswabs_ hold what the last step_radiation / prep_radiation left (and downloaded);
+  // sw_armed_: ... to the host arrays sw_host_ (cice_radiation_chain mode 1).  Whatever else writes those five buffers
+  // ends both (forget_sw).
+  DevBuf<double> rad_b_;
+  bool sw_resident_ = false, sw_armed_ = false;
+  int rad_mode_ = 0;
+  const double* sw_host_[5] = {};
+  void forget_sw() { sw_resident_ = false; sw_armed_ = false; }
+  void keep_sw(const double* fswsfc, const double* fswint, const double* fswthrun, const double* Sswabs, const double* Iswabs);
+  hipEvent_t rad_ev_[4] = {};
+  bool rad_timed_ = false;
+  float rad_ms_[2] = {0, 0};
   hipEvent_t ho_ev_[2] = {};                 // around k_state_from_transport (handover_time)
   bool ho_timed_ = false, ho_pending_ = false;
   float ho_ms_ = 0.0f;

@@ -47,6 +47,8 @@ ColumnBatch::~ColumnBatch() {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ho_ev_)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : rad_ev_)
+    if (e) (void)hipEventDestroy(e);
 }
 
 // Every field of cice_thermo_fields, once, in the order the fields travel: what alloc sizes, upload and download move
@@ -79,6 +81,7 @@ void ColumnBatch::alloc(hipStream_t stream, CopyFan& fan, int nx, int ny, int nb
   nx_ = nx; ny_ = ny; nb_ = nb;
   kept_aicen_init_ = false;
   therm2_state_ = false;
+  forget_sw();
   const size_t np = (size_t)nx * ny, n2 = np * nb, nc = n2 * NCAT;
   std::vector<int32_t> hb;
   if (dom && same_layout(*dom)) {
@@ -110,13 +113,16 @@ void ColumnBatch::tracer_copy(int it, const double* from, double* to, hipMemcpyK
   CICE_HIP(hipMemcpy2DAsync(to + o, pitch, from + o, pitch, np * 8, (size_t)NCAT * nb_, kind, cs()));
 }
 
-void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef) {
+void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef,
+                                bool with_sw) {
   const size_t n2 = (size_t)nx_ * ny_ * nb_;
   const std::vector<Field> fs = fields(h);
   for (const Field& x : fs) {
     if (!(x.dir & F_UP)) continue;
     if (!with_fbot_tbot && (x.name == A_FBOT || x.name == A_TBOT)) continue;   // produced on the device
     if (!with_coef && (x.name == A_LH || x.name == A_SH)) continue;            // likewise (atmo_boundary_layer)
+    if (!with_sw && (x.name == A_FSWSFC || x.name == A_FSWINT || x.name == A_FSWTHRU || x.name == A_SSW || x.name == A_ISW))
+      continue;                                                                // left there by the radiation stage
     CICE_REQUIRE(x.h != nullptr, "cice_thermo_batch_upload: NULL field");
     if (x.name == A_TRCRN && tp) {
       // of trcrn(nx, ny, max_ntrcr, ncat, nblocks) the column physics reads and writes the surface temperature only:
@@ -136,6 +142,7 @@ void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields
 void ColumnBatch::upload(const ThermoParams* tp, const cice_thermo_fields* h) {
   kept_aicen_init_ = false;
   therm2_state_ = false;
+  forget_sw();
   upload_fields(tp, h, true, true);
   CICE_HIP(hipStreamSynchronize(stream_));
 }
@@ -198,6 +205,7 @@ void ColumnBatch::step(const ThermoParams* tp, double dt, double yday, long long
                        int32_t* jstop, int32_t* nstop, int32_t* bstop, float* elapsed_ms) {
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
   therm2_state_ = false;
+  forget_sw();                         // the column update writes the shortwave buffers
   unsigned long long h[THERMO_STATUS_WORDS];
   hipEvent_t ev[2] = {nullptr, nullptr};
   launch_step(*tp, dt, yday, h, elapsed_ms, ev);
@@ -282,10 +290,15 @@ void ColumnBatch::step_therm1(const ThermoParams* tp, double chio, double dt, do
   CICE_REQUIRE(fz->aice && fz->frzmlt && fz->sst && fz->Tf && fz->strocnxT && fz->strocnyT, "NULL frzmlt input");
   hipStream_t s = stream_;
   therm2_state_ = false;
+  // cice_radiation_chain: the five shortwave arrays are on the device already if they are the host arrays the radiation
+  // stage downloaded to; consumed or not, the record ends here (the column update writes those buffers)
+  const bool sw_kept = sw_armed_ && st->fswsfc == sw_host_[0] && st->fswint == sw_host_[1] && st->fswthrun == sw_host_[2] &&
+                       st->Sswabs == sw_host_[3] && st->Iswabs == sw_host_[4];
+  forget_sw();
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
   // every upload first, spread over the side streams (about 150 separate host arrays), then the kernels
   fan_->fork(s);
-  upload_fields(tp, st, false, atm == nullptr);
+  upload_fields(tp, st, false, atm == nullptr, !sw_kept);
   if (atm) {
     CICE_REQUIRE(atm->uatm && atm->vatm && atm->wind && atm->zlvl, "NULL atmosphere input");
     CICE_REQUIRE(atm->calc_strair || (atm->strax && atm->stray), "calc_strair = F needs strax, stray");
@@ -706,6 +719,165 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
   CICE_HIP(hipStreamSynchronize(s));
   for (int k = 0; k < CLEAN_TIMES && timed; ++k) CICE_HIP(hipEventElapsedTime(&clean_ms_[k], clean_ev_[k], clean_ev_[k + 1]));
   therm2_state_ = true;
+}
+
+// planes of rad_b_: the 2-d fields (nx, ny, nb each), then six (nx, ny, ncat, nb) arrays -- step_radiation's albedo outputs;
+// prep_radiation keeps its copy of aicen in the first of them
+enum { R_SWVDR = 0, R_SWVDF, R_SWIDR, R_SWIDF, R_OCN, R_GBM, R_AICE = R_GBM + 4, R_SF, R_FAC, R_2D };
+
+void ColumnBatch::keep_sw(const double* fswsfc, const double* fswint, const double* fswthrun, const double* Sswabs,
+                          const double* Iswabs) {
+  sw_resident_ = true;
+  sw_armed_ = rad_mode_ == 1;
+  const double* h[5] = {fswsfc, fswint, fswthrun, Sswabs, Iswabs};
+  for (int k = 0; k < 5; ++k) sw_host_[k] = h[k];
+}
+
+// step_radiation (ice_step_mod.F90:764-973) for shortwave = 'default' on the batch: see include/cice4_amd.h
+void ColumnBatch::step_radiation(const ThermoParams* tp, const ShortwaveParams* sp, const cice_radiation_fields* f) {
+  CICE_REQUIRE(tp, "cice_thermo_init has not been called");
+  CICE_REQUIRE(sp, "cice_shortwave_init has not been called");
+  CICE_REQUIRE(f->state_resident == 0 || f->state_resident == 1, "cice_step_radiation: state_resident must be 0 or 1");
+  const bool resident = f->state_resident == 1;
+  CICE_REQUIRE(!resident || therm2_state_,
+               "cice_step_radiation: state_resident needs a cice_step_ridge or cice_step_therm2_cleanup on this batch in front");
+  CICE_REQUIRE(resident || (f->aicen && f->trcrn && f->vicen && f->vsnon), "cice_step_radiation: NULL state");
+  CICE_REQUIRE(f->alvdrn && f->alidrn && f->alvdfn && f->alidfn && f->albicen && f->albsnon && f->fswsfcn && f->fswintn &&
+                   f->fswthrun && f->Sswabsn && f->Iswabsn, "cice_step_radiation: NULL output");
+  hipStream_t s = stream_;
+  forget_sw();
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  if (rad_b_.n != R_2D * n2 + 6 * nc) rad_b_.alloc(R_2D * n2 + 6 * nc);
+  auto d2 = [&](int k) { return rad_b_.p + (size_t)k * n2; };
+  auto dc = [&](int k) { return rad_b_.p + R_2D * n2 + (size_t)k * nc; };
+  double* const alb[4] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn};
+  auto down_sw = [&] {
+    fswsfc_.download(f->fswsfcn, cs()); fswint_.download(f->fswintn, cs()); fswthrun_.download(f->fswthrun, cs());
+    Sswabs_.download(f->Sswabsn, cs()); Iswabs_.download(f->Iswabsn, cs());
+  };
+  if (!tp->calc_Tsfc) {                // "initialize for safety" (:946-967): albicen, albsnon, coszen are not touched
+    CICE_HIP(hipMemsetAsync(dc(0), 0, 4 * nc * 8, s));
+    fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
+    fan_->fork(s);
+    for (int k = 0; k < 4; ++k) CICE_HIP(hipMemcpyAsync(alb[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
+    down_sw();
+    fan_->join();
+    CICE_HIP(hipStreamSynchronize(s));
+    keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+    return;
+  }
+  CICE_REQUIRE(f->swvdr && f->swvdf && f->swidr && f->swidf, "cice_step_radiation: NULL forcing");
+  fan_->fork(s);
+  if (!resident) {                     // of the state the scheme reads these four; the rest of the batch's state is stale now
+    therm2_state_ = false;
+    aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
+    tracer_copy(tp->nt_Tsfc - 1, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
+  }
+  const double* in2[5] = {f->swvdr, f->swvdf, f->swidr, f->swidf, f->ocn_albedo};
+  for (int k = 0; k < 5; ++k)
+    if (in2[k]) CICE_HIP(hipMemcpyAsync(d2(R_SWVDR + k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  fan_->join();
+  ShortwaveArgs a{};
+  a.p = *sp;
+  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.tsfc_planes = NTRCR;
+  a.blk = blk_.p;
+  a.aicen = aicen_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.Tsfc = trcrn_.p + (size_t)(tp->nt_Tsfc - 1) * np;
+  a.swvdr = d2(R_SWVDR); a.swvdf = d2(R_SWVDF); a.swidr = d2(R_SWIDR); a.swidf = d2(R_SWIDF);
+  a.ocn_albedo = f->ocn_albedo ? d2(R_OCN) : nullptr;
+  a.alvdrn = dc(0); a.alidrn = dc(1); a.alvdfn = dc(2); a.alidfn = dc(3); a.albicen = dc(4); a.albsnon = dc(5);
+  a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Iswabsn = Iswabs_.p; a.Sswabsn = Sswabs_.p;
+  const bool timed = rad_timed_;
+  for (int k = 0; k < 2 && timed; ++k)
+    if (!rad_ev_[k]) CICE_HIP(hipEventCreate(&rad_ev_[k]));
+  if (timed) CICE_HIP(hipEventRecord(rad_ev_[0], s));
+  shortwave_launch(a, s);
+  if (timed) CICE_HIP(hipEventRecord(rad_ev_[1], s));
+  fan_->fork(s);
+  double* const out6[6] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon};
+  for (int k = 0; k < 6; ++k) CICE_HIP(hipMemcpyAsync(out6[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
+  down_sw();
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  if (timed) CICE_HIP(hipEventElapsedTime(&rad_ms_[0], rad_ev_[0], rad_ev_[1]));
+  if (f->coszen)                       // "sun above the horizon" (:843), every cell of every block
+    for (size_t q = 0; q < n2; ++q) f->coszen[q] = K::p5;
+  keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+}
+
+// prep_radiation (ice_step_mod.F90:84-218) on the batch: see include/cice4_amd.h
+void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiation_fields* f) {
+  CICE_REQUIRE(tp, "cice_thermo_init has not been called");
+  CICE_REQUIRE(f->sw_resident == 0 || f->sw_resident == 1, "cice_prep_radiation: sw_resident must be 0 or 1");
+  const bool resident = f->sw_resident == 1;
+  CICE_REQUIRE(!resident || sw_resident_,
+               "cice_prep_radiation: sw_resident needs a cice_step_radiation on this batch in front");
+  CICE_REQUIRE(f->fswsfcn && f->fswintn && f->fswthrun && f->Sswabsn && f->Iswabsn, "cice_prep_radiation: NULL field");
+  hipStream_t s = stream_;
+  forget_sw();
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  if (rad_b_.n != R_2D * n2 + 6 * nc) rad_b_.alloc(R_2D * n2 + 6 * nc);
+  auto d2 = [&](int k) { return rad_b_.p + (size_t)k * n2; };
+  double* const daicen = rad_b_.p + R_2D * n2;
+  auto down_sw = [&] {
+    fswsfc_.download(f->fswsfcn, cs()); fswint_.download(f->fswintn, cs()); fswthrun_.download(f->fswthrun, cs());
+    Sswabs_.download(f->Sswabsn, cs()); Iswabs_.download(f->Iswabsn, cs());
+  };
+  if (!tp->calc_Tsfc) {                // "initialize for safety" (:195-212)
+    fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
+    fan_->fork(s);
+    down_sw();
+    fan_->join();
+    CICE_HIP(hipStreamSynchronize(s));
+    keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+    return;
+  }
+  CICE_REQUIRE(f->swvdr && f->swvdf && f->swidr && f->swidf && f->alvdr_gbm && f->alvdf_gbm && f->alidr_gbm &&
+                   f->alidf_gbm && f->aice && f->scale_factor && f->fswfac && f->aicen, "cice_prep_radiation: NULL field");
+  fan_->fork(s);
+  const double* in2[10] = {f->swvdr, f->swvdf, f->swidr, f->swidf, nullptr, f->alvdr_gbm, f->alvdf_gbm, f->alidr_gbm,
+                           f->alidf_gbm, f->aice};
+  static_assert(R_AICE == 9 && R_SF == 10 && R_FAC == 11, "order of in2");
+  for (int k = 0; k < 10; ++k)
+    if (in2[k]) CICE_HIP(hipMemcpyAsync(d2(k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  CICE_HIP(hipMemcpyAsync(d2(R_SF), f->scale_factor, n2 * 8, hipMemcpyHostToDevice, cs()));
+  CICE_HIP(hipMemcpyAsync(d2(R_FAC), f->fswfac, n2 * 8, hipMemcpyHostToDevice, cs()));   // (kept off the physical cells)
+  CICE_HIP(hipMemcpyAsync(daicen, f->aicen, nc * 8, hipMemcpyHostToDevice, cs()));
+  if (!resident) {
+    fswsfc_.upload(f->fswsfcn, cs()); fswint_.upload(f->fswintn, cs()); fswthrun_.upload(f->fswthrun, cs());
+    Sswabs_.upload(f->Sswabsn, cs()); Iswabs_.upload(f->Iswabsn, cs());
+  }
+  fan_->join();
+  PrepRadiationArgs a{};
+  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.blk = blk_.p;
+  a.swvdr = d2(R_SWVDR); a.swvdf = d2(R_SWVDF); a.swidr = d2(R_SWIDR); a.swidf = d2(R_SWIDF);
+  a.alvdr_gbm = d2(R_GBM); a.alvdf_gbm = d2(R_GBM + 1); a.alidr_gbm = d2(R_GBM + 2); a.alidf_gbm = d2(R_GBM + 3);
+  a.aice = d2(R_AICE); a.aicen = daicen; a.scale_factor = d2(R_SF); a.fswfac = d2(R_FAC);
+  a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Sswabsn = Sswabs_.p; a.Iswabsn = Iswabs_.p;
+  const bool timed = rad_timed_;
+  for (int k = 2; k < 4 && timed; ++k)
+    if (!rad_ev_[k]) CICE_HIP(hipEventCreate(&rad_ev_[k]));
+  if (timed) CICE_HIP(hipEventRecord(rad_ev_[2], s));
+  prep_radiation_launch(a, s);
+  if (timed) CICE_HIP(hipEventRecord(rad_ev_[3], s));
+  fan_->fork(s);
+  CICE_HIP(hipMemcpyAsync(f->scale_factor, d2(R_SF), n2 * 8, hipMemcpyDeviceToHost, cs()));
+  CICE_HIP(hipMemcpyAsync(f->fswfac, d2(R_FAC), n2 * 8, hipMemcpyDeviceToHost, cs()));
+  down_sw();
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  if (timed) CICE_HIP(hipEventElapsedTime(&rad_ms_[1], rad_ev_[2], rad_ev_[3]));
+  keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+}
+
+void ColumnBatch::radiation_chain(int mode) {
+  CICE_REQUIRE(mode == 0 || mode == 1, "cice_radiation_chain: mode must be 0 or 1");
+  rad_mode_ = mode;
+  sw_armed_ = false;
+}
+
+void ColumnBatch::radiation_times(bool enable, float ms[2]) {
+  rad_timed_ = enable;
+  for (int k = 0; k < 2 && ms; ++k) ms[k] = rad_ms_[k];
 }
 
 void ColumnBatch::handover_time(bool enable, float* ms) {

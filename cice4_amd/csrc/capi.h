@@ -20,6 +20,7 @@
 #include "therm.h"
 #include "itd.h"
 #include "ridge.h"
+#include "shortwave.h"
 #include "transport.h"
 #include "batch.h"
 
@@ -124,6 +125,11 @@ struct cice_ctx {
   RidgeParams rp{};
   bool have_ridge = false;
   DevBuf<unsigned long long> ridge_w;
+  // shortwave (shortwave.h): the namelist values given to cice_shortwave_init; staging and list of the block-wise entry
+  ShortwaveParams sp{};
+  bool have_sw = false;
+  DevBuf<double> sw_d;
+  DevBuf<int32_t> sw_i;
   // device is required lazily: domain queries work on a CPU-only host
   // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
   // process may have changed the current device since the last call (another context on another GPU,

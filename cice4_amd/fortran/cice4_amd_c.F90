@@ -620,6 +620,70 @@ module cice4_amd_c
       end function
    end interface
 
+   ! shortwave radiation, shortwave = 'default' (source/ice_shortwave.F90: shortwave_ccsm3; cice4_amd/csrc/shortwave.hip) and
+   ! the drivers prep_radiation, step_radiation (source/ice_step_mod.F90:84-218, :764-973)
+   type, bind(C) :: cice_shortwave_config
+      integer(c_int) :: shortwave, albedo_type
+      real(c_double) :: albicev, albicei, albsnowv, albsnowi, ahmax
+      real(c_double) :: albocn, dT_mlt, dalb_mlt, snowpatch
+      real(c_double) :: awtvdr, awtidr, awtvdf, awtidf
+   end type
+
+   type, bind(C) :: cice_radiation_fields
+      integer(c_int) :: ncat, state_resident
+      type(c_ptr) :: aicen, trcrn, vicen, vsnon
+      type(c_ptr) :: swvdr, swvdf, swidr, swidf, ocn_albedo
+      type(c_ptr) :: alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, fswsfcn, fswintn, fswthrun
+      type(c_ptr) :: Sswabsn, Iswabsn
+      type(c_ptr) :: coszen
+   end type
+
+   type, bind(C) :: cice_prep_radiation_fields
+      integer(c_int) :: ncat, sw_resident
+      type(c_ptr) :: swvdr, swvdf, swidr, swidf, alvdr_gbm, alvdf_gbm, alidr_gbm, alidf_gbm, aice
+      type(c_ptr) :: scale_factor
+      type(c_ptr) :: fswfac
+      type(c_ptr) :: fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn
+      type(c_ptr) :: aicen
+   end type
+
+   interface
+      integer(c_int) function cice_shortwave_init(ctx, cfg) bind(C, name='cice_shortwave_init')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_shortwave_config), intent(in) :: cfg
+      end function
+      ! ocn_albedo: c_loc of the array (-DAusCOM) or c_null_ptr
+      integer(c_int) function cice_shortwave_ccsm3(ctx, nx_block, ny_block, icells, indxi, indxj, aicen, vicen, vsnon, Tsfcn, &
+            swvdr, swvdf, swidr, swidf, alvdrn, alidrn, alvdfn, alidfn, fswsfc, fswint, fswthru, Iswabs, albin, albsn, &
+            ocn_albedo) bind(C, name='cice_shortwave_ccsm3')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, icells
+         integer(c_int), intent(in) :: indxi(*), indxj(*)
+         real(c_double), intent(in) :: aicen(*), vicen(*), vsnon(*), Tsfcn(*), swvdr(*), swvdf(*), swidr(*), swidf(*)
+         real(c_double), intent(out) :: alvdrn(*), alidrn(*), alvdfn(*), alidfn(*), fswsfc(*), fswint(*), fswthru(*), &
+                                        Iswabs(*), albin(*), albsn(*)
+         type(c_ptr), value :: ocn_albedo
+      end function
+      integer(c_int) function cice_step_radiation(ctx, f) bind(C, name='cice_step_radiation')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_radiation_fields), intent(in) :: f
+      end function
+      integer(c_int) function cice_prep_radiation(ctx, f) bind(C, name='cice_prep_radiation')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_prep_radiation_fields), intent(in) :: f
+      end function
+      ! radiation -> step_therm1 without the upload of the five shortwave arrays: mode 0 off, 1 on
+      integer(c_int) function cice_radiation_chain(ctx, mode) bind(C, name='cice_radiation_chain')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: mode
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

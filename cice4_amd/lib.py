@@ -124,6 +124,30 @@ class RidgeFields(C.Structure):
     _fields_ = [("ncat", C.c_int), ("bound", C.c_int)] + [(n, C.c_void_p) for n in RIDGE_PTRS]
 
 
+class ShortwaveConfig(C.Structure):
+    _fields_ = [("shortwave", C.c_int), ("albedo_type", C.c_int)] + [
+        (n, C.c_double) for n in ("albicev", "albicei", "albsnowv", "albsnowi", "ahmax", "albocn", "dT_mlt", "dalb_mlt",
+                                  "snowpatch", "awtvdr", "awtidr", "awtvdf", "awtidf")]
+
+
+RADIATION_STATE = ("aicen", "trcrn", "vicen", "vsnon")
+RADIATION_IN = ("swvdr", "swvdf", "swidr", "swidf", "ocn_albedo")
+RADIATION_OUT = ("alvdrn", "alidrn", "alvdfn", "alidfn", "albicen", "albsnon", "fswsfcn", "fswintn", "fswthrun", "Sswabsn",
+                 "Iswabsn")
+RADIATION_SW = ("fswsfcn", "fswintn", "fswthrun", "Sswabsn", "Iswabsn")
+PREP_RADIATION_PTRS = ("swvdr", "swvdf", "swidr", "swidf", "alvdr_gbm", "alvdf_gbm", "alidr_gbm", "alidf_gbm", "aice",
+                       "scale_factor", "fswfac") + RADIATION_SW + ("aicen",)
+
+
+class RadiationFields(C.Structure):
+    _fields_ = [("ncat", C.c_int), ("state_resident", C.c_int)] + [
+        (n, C.c_void_p) for n in RADIATION_STATE + RADIATION_IN + RADIATION_OUT + ("coszen",)]
+
+
+class PrepRadiationFields(C.Structure):
+    _fields_ = [("ncat", C.c_int), ("sw_resident", C.c_int)] + [(n, C.c_void_p) for n in PREP_RADIATION_PTRS]
+
+
 class ThermoFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in THERMO_STATE + THERMO_FORCING + THERMO_CAT_IN + THERMO_SW
                 + THERMO_OUT + THERMO_ONSET]
@@ -953,6 +977,60 @@ class Context:
         ms = (C.c_float * len(RIDGE_TIMES))()
         self._ck(self.lib.cice_ridge_times(self.h, int(enable), ms))
         return dict(zip(RIDGE_TIMES, ms))
+
+    # ---- shortwave radiation, shortwave = 'default' (ice_shortwave: shortwave_ccsm3) ---------
+    SHORTWAVE_OUT = ("alvdrn", "alidrn", "alvdfn", "alidfn", "fswsfc", "fswint", "fswthru", "Iswabs", "albin", "albsn")
+
+    def shortwave_init(self, shortwave="default", albedo_type="default", albicev=0.78, albicei=0.36, albsnowv=0.98,
+                       albsnowi=0.70, ahmax=0.3, albocn=0.06, dT_mlt=1.0, dalb_mlt=-0.075, snowpatch=0.02,
+                       awtvdr=0.00318, awtidr=0.00182, awtvdf=0.63282, awtidf=0.36218):
+        """cice_shortwave_init (after thermo_init, which gives heat_capacity, calc_Tsfc, nt_Tsfc).  The defaults are the
+        reference's namelist defaults and the stand-alone build's parameters.  shortwave='dEdd' raises CiceError with
+        code CICE_EUNSUPPORTED."""
+        cfg = ShortwaveConfig({"default": 0, "dEdd": 1}[shortwave], {"default": 0, "constant": 1}[albedo_type], albicev,
+                              albicei, albsnowv, albsnowi, ahmax, albocn, dT_mlt, dalb_mlt, snowpatch, awtvdr, awtidr,
+                              awtvdf, awtidf)
+        self._ck(self.lib.cice_shortwave_init(self.h, C.byref(cfg)))
+
+    def shortwave_ccsm3(self, icells, indxi, indxj, a, ocn_albedo=None):
+        """cice_shortwave_ccsm3 on one block and category.  a: aicen, vicen, vsnon, Tsfcn, swvdr, swvdf, swidr, swidf
+        (ny,nx) in; the arrays of SHORTWAVE_OUT ((ny,nx), Iswabs (nilyr,ny,nx)) are written on the whole block.
+        ocn_albedo: the -DAusCOM build's last argument, None = absent."""
+        ny, nx = a["aicen"].shape
+        self._ck(self.lib.cice_shortwave_ccsm3(
+            self.h, nx, ny, icells, _i4(indxi), _i4(indxj),
+            *[_f8(a[k]) for k in ("aicen", "vicen", "vsnon", "Tsfcn", "swvdr", "swvdf", "swidr", "swidf")],
+            *[_f8(a[k]) for k in self.SHORTWAVE_OUT], _f8(ocn_albedo)))
+
+    def step_radiation(self, a, state_resident=False):
+        """cice_step_radiation on the batch (thermo_batch_alloc).  a: swvdr, swvdf, swidr, swidf (nb,ny,nx), the arrays of
+        RADIATION_OUT, and -- unless state_resident -- aicen, trcrn, vicen, vsnon; optional ocn_albedo, coszen."""
+        f = RadiationFields()
+        f.ncat, f.state_resident = NCAT, int(state_resident)
+        for n, _t in RadiationFields._fields_[2:]:
+            setattr(f, n, _f8(a[n]) if a.get(n) is not None else None)
+        self._ck(self.lib.cice_step_radiation(self.h, C.byref(f)))
+
+    def prep_radiation(self, a, sw_resident=False):
+        """cice_prep_radiation on the batch.  a: the arrays of PREP_RADIATION_PTRS; scale_factor, fswfac and the five
+        shortwave arrays are updated in place (sw_resident: the device copies are scaled, the five are written only)."""
+        f = PrepRadiationFields()
+        f.ncat, f.sw_resident = NCAT, int(sw_resident)
+        for n in PREP_RADIATION_PTRS:
+            setattr(f, n, _f8(a[n]) if a.get(n) is not None else None)
+        self._ck(self.lib.cice_prep_radiation(self.h, C.byref(f)))
+
+    def radiation_chain(self, mode):
+        """cice_radiation_chain: 0 off; 1: a step_therm1 that follows a step_radiation / prep_radiation and is given the
+        SAME five arrays fswsfc, fswint, fswthrun, Sswabs, Iswabs those calls downloaded to uploads none of them."""
+        self._ck(self.lib.cice_radiation_chain(self.h, int(mode)))
+
+    def radiation_times(self, enable=True):
+        """cice_radiation_times: switch the event timing on / off; (k_shortwave_ccsm3, k_prep_radiation) ms of the last
+        timed calls"""
+        ms = (C.c_float * 2)()
+        self._ck(self.lib.cice_radiation_times(self.h, int(enable), ms))
+        return tuple(ms)
 
     def therm2_itd_times(self, enable=True):
         """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""

@@ -691,6 +691,81 @@ int cice_step_ridge(cice_ctx *ctx, double dt, const cice_ridge_fields *f, int32_
  * not queued: a call queues them three at a time while a block asks for more), ms[40] the diagnostics. */
 int cice_ridge_times(cice_ctx *ctx, int enable, float ms[41]);
 
+/* ---- shortwave radiation, shortwave = 'default' (ccsm3) (source/ice_shortwave.F90: shortwave_ccsm3 :364-541 with
+ * compute_albedos, constant_albedos, absorbed_solar; the drivers prep_radiation and step_radiation of
+ * source/ice_step_mod.F90:84-218, :764-973) on the device ----
+ * cice_shortwave_init: the namelist's values.  shortwave: 0 'default'; 1 'dEdd' is CICE_EUNSUPPORTED (delta-Eddington is
+ * not built).  albedo_type: 0 'default', 1 'constant'.  albocn, dT_mlt, dalb_mlt, snowpatch: parameters of the
+ * stand-alone build (ice_constants albocn = 0.06; 1, -0.075, 0.02), namelist variables under -DAusCOM.  awt*: the
+ * weights of ice_constants.  kappav, i0vis, Timelt, puny are the reference's constants.  heat_capacity, calc_Tsfc and
+ * nt_Tsfc are those of cice_thermo_init: CICE_EINVAL without that call, CICE_EUNSUPPORTED with heat_capacity = 0 (that
+ * branch of absorbed_solar assumes nilyr = 1). */
+typedef struct {
+  int shortwave, albedo_type;
+  double albicev, albicei, albsnowv, albsnowi, ahmax;
+  double albocn, dT_mlt, dalb_mlt, snowpatch;
+  double awtvdr, awtidr, awtvdf, awtidf;
+} cice_shortwave_config;
+int cice_shortwave_init(cice_ctx *ctx, const cice_shortwave_config *cfg);
+/* Drop-in for `call shortwave_ccsm3(...)`: one block, one category, host pointers, the reference's argument order; all
+ * arrays (nx_block,ny_block), Iswabs (nx_block,ny_block,nilyr).  ocn_albedo: the -DAusCOM build's last argument, NULL =
+ * absent (the scalar albocn).  Every output is written on the whole block: what the reference's initialisation leaves
+ * off the list (the ocean albedo in the four albedos, zero elsewhere).  exp is glibc's restated; atan(hi*c4) is the
+ * device library's (<= 1 ulp), so outputs of cells with hi < ahmax agree to ~1e-15, all others bit for bit. */
+int cice_shortwave_ccsm3(cice_ctx *ctx, int nx_block, int ny_block, int icells, const int32_t *indxi,
+                         const int32_t *indxj, const double *aicen, const double *vicen, const double *vsnon,
+                         const double *Tsfcn, const double *swvdr, const double *swvdf, const double *swidr,
+                         const double *swidf, double *alvdrn, double *alidrn, double *alvdfn, double *alidfn,
+                         double *fswsfc, double *fswint, double *fswthru, double *Iswabs, double *albin, double *albsn,
+                         const double *ocn_albedo);
+/* step_radiation as ONE call on the batch of cice_thermo_batch_alloc, all blocks and categories: the list of a
+ * (category, block) is aicen > puny on the block's physical cells.  sw*, ocn_albedo (may be NULL), coszen (nx,ny,nb);
+ * the nine per-category outputs (nx,ny,ncat,nb); Sswabsn, Iswabsn as Sswabs, Iswabs of cice_thermo_fields.
+ * state_resident = 1: aicen, vicen, vsnon and the surface temperature are what cice_step_ridge or
+ *   cice_step_therm2_cleanup left on the device (the record cice_step_therm2_cleanup's state_resident = 1 checks:
+ *   CICE_EINVAL without it); the state pointers are not read and the record stays.
+ * state_resident = 0: aicen, vicen, vsnon and the nt_Tsfc plane of trcrn are uploaded (which ends that record: the
+ *   batch no longer holds one call's whole state).
+ * One download of the outputs at the end; coszen, where non-NULL, is set to 0.5.  The results also stay in the batch's
+ * shortwave buffers, the ones cice_step_therm1 reads (cice_prep_radiation's sw_resident, cice_radiation_chain).
+ * calc_Tsfc = 0: the four albedos, fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn are zero-filled; albicen, albsnon and
+ * coszen are left alone, as in the reference. */
+typedef struct {
+  int ncat, state_resident;
+  const double *aicen, *trcrn, *vicen, *vsnon;
+  const double *swvdr, *swvdf, *swidr, *swidf, *ocn_albedo;
+  double *alvdrn, *alidrn, *alvdfn, *alidfn, *albicen, *albsnon, *fswsfcn, *fswintn, *fswthrun;
+  double *Sswabsn, *Iswabsn;
+  double *coszen;
+} cice_radiation_fields;
+int cice_step_radiation(cice_ctx *ctx, const cice_radiation_fields *f);
+/* prep_radiation as ONE call: on the physical cells scale_factor = netsw / scale_factor where aice > 0 and
+ * scale_factor > puny, else 1, and fswfac = scale_factor; then the five per-category shortwave arrays times the cell's
+ * new scale_factor on the cells with aicen > puny.  2-d fields (nx,ny,nb).
+ * sw_resident = 1: the device copies the last cice_step_radiation (or cice_prep_radiation) left are scaled, the five
+ *   host arrays are download targets only; CICE_EINVAL if the batch holds none.  sw_resident = 0: they are uploaded.
+ * One download at the end: scale_factor, fswfac, the five.  calc_Tsfc = 0: the five are zero-filled, nothing else. */
+typedef struct {
+  int ncat, sw_resident;
+  const double *swvdr, *swvdf, *swidr, *swidf, *alvdr_gbm, *alvdf_gbm, *alidr_gbm, *alidf_gbm, *aice;
+  double *scale_factor; /* in / out */
+  double *fswfac;       /* out */
+  double *fswsfcn, *fswintn, *fswthrun, *Sswabsn, *Iswabsn; /* in / out */
+  const double *aicen;
+} cice_prep_radiation_fields;
+int cice_prep_radiation(cice_ctx *ctx, const cice_prep_radiation_fields *f);
+/* radiation -> step_therm1 WITHOUT the upload of the shortwave arrays.  mode 0 (the default) is off, 1 is on, other
+ * values are CICE_EINVAL.  On: a cice_step_radiation or cice_prep_radiation that returns CICE_OK records the five host
+ * arrays its shortwave results were downloaded to; the next cice_step_therm1 / cice_step_therm1_abl on the batch whose
+ * state->fswsfc, fswint, fswthrun, Sswabs, Iswabs are those arrays uploads none of them (8 planes per category).  Every
+ * other write to those device buffers ends the record: cice_thermo_batch_upload, cice_thermo_batch_step, a new
+ * cice_thermo_batch_alloc, and every cice_step_therm1* call, consumed or not.  Nothing is deferred: the host arrays are
+ * valid at every moment.  The caller's part: nothing writes to those five host arrays between the two calls. */
+int cice_radiation_chain(cice_ctx *ctx, int mode);
+/* Measurement aid (scripts/radiation_cost.py), off by default: ms[0], ms[1] the device times (ms) of the last timed
+ * k_shortwave_ccsm3 and k_prep_radiation. */
+int cice_radiation_times(cice_ctx *ctx, int enable, float ms[2]);
+
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
  * dependencies from ntrcr / trcr_depend (ice_init.F90:848-852: 0 area tracer, 1 ice-volume, 2 snow-volume tracer),
