@@ -7,6 +7,7 @@
 
 #include "atmo.h"
 #include "cleanup.h"
+#include "dedd.h"
 #include "common.h"
 #include "domain.h"
 #include "halo.h"
@@ -110,6 +111,9 @@ class ColumnBatch {
   // step_radiation / prep_radiation for shortwave = 'default' (shortwave.h); sp: the parameters of cice_shortwave_init
   void step_radiation(const ThermoParams* tp, const ShortwaveParams* sp, const cice_radiation_fields* f);
   void prep_radiation(const ThermoParams* tp, const cice_prep_radiation_fields* f);
+  // step_radiation for shortwave = 'dEdd' (dedd.h); dp: the parameters of cice_shortwave_dedd_init
+  void step_radiation_dedd(const ThermoParams* tp, const DeddParams* dp, const cice_radiation_dedd_fields* f);
+  void dedd_times(bool enable, float ms[1]);        // the last timed k_shortwave_dedd
   void radiation_chain(int mode);                   // cice_radiation_chain
   void radiation_times(bool enable, float ms[2]);   // the last timed k_shortwave_ccsm3, k_prep_radiation
   void handover_time(bool enable, float* ms);       // the last timed k_state_from_transport (0: none since enabled)
@@ -196,6 +200,11 @@ class ColumnBatch {
   hipEvent_t rad_ev_[4] = {};
   bool rad_timed_ = false;
   float rad_ms_[2] = {0, 0};
+  // delta-Eddington: coszen and the four sw fields, the seven albedo outputs, apondn and hpondn
+  DevBuf<double> dedd_b_;
+  hipEvent_t dedd_ev_[2] = {};
+  bool dedd_timed_ = false;
+  float dedd_ms_ = 0.0f;
   hipEvent_t ho_ev_[2] = {};                 // around k_state_from_transport (handover_time)
   bool ho_timed_ = false, ho_pending_ = false;
   float ho_ms_ = 0.0f;

@@ -49,6 +49,8 @@ ColumnBatch::~ColumnBatch() {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : rad_ev_)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : dedd_ev_)
+    if (e) (void)hipEventDestroy(e);
 }
 
 // Every field of cice_thermo_fields, once, in the order the fields travel: what alloc sizes, upload and download move
@@ -867,6 +869,89 @@ void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiati
   CICE_HIP(hipStreamSynchronize(s));
   if (timed) CICE_HIP(hipEventElapsedTime(&rad_ms_[1], rad_ev_[2], rad_ev_[3]));
   keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+}
+
+// planes of dedd_b_: coszen and the four sw fields (nx, ny, nb each), then nine (nx, ny, ncat, nb) arrays -- the four
+// albedos, albicen, albsnon, albpndn, and the inputs apondn, hpondn
+enum { D_COSZEN = 0, D_SWVDR, D_SWVDF, D_SWIDR, D_SWIDF, D_2D };
+
+// step_radiation (ice_step_mod.F90:764-973) for shortwave = 'dEdd' on the batch: see include/cice4_amd.h
+void ColumnBatch::step_radiation_dedd(const ThermoParams* tp, const DeddParams* dp, const cice_radiation_dedd_fields* f) {
+  CICE_REQUIRE(tp, "cice_thermo_init has not been called");
+  CICE_REQUIRE(dp, "cice_shortwave_dedd_init has not been called");
+  CICE_REQUIRE(f->state_resident == 0 || f->state_resident == 1, "cice_step_radiation_dedd: state_resident must be 0 or 1");
+  const bool resident = f->state_resident == 1;
+  CICE_REQUIRE(!resident || therm2_state_,
+               "cice_step_radiation_dedd: state_resident needs a cice_step_ridge or cice_step_therm2_cleanup on this batch in front");
+  CICE_REQUIRE(resident || (f->aicen && f->trcrn && f->vicen && f->vsnon), "cice_step_radiation_dedd: NULL state");
+  CICE_REQUIRE(f->alvdrn && f->alidrn && f->alvdfn && f->alidfn && f->albicen && f->albsnon && f->albpndn && f->fswsfcn &&
+                   f->fswintn && f->fswthrun && f->Sswabsn && f->Iswabsn, "cice_step_radiation_dedd: NULL output");
+  hipStream_t s = stream_;
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  if (dedd_b_.n != D_2D * n2 + 9 * nc) dedd_b_.alloc(D_2D * n2 + 9 * nc);
+  auto d2 = [&](int k) { return dedd_b_.p + (size_t)k * n2; };
+  auto dc = [&](int k) { return dedd_b_.p + D_2D * n2 + (size_t)k * nc; };
+  double* const alb[4] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn};
+  auto down_sw = [&] {
+    fswsfc_.download(f->fswsfcn, cs()); fswint_.download(f->fswintn, cs()); fswthrun_.download(f->fswthrun, cs());
+    Sswabs_.download(f->Sswabsn, cs()); Iswabs_.download(f->Iswabsn, cs());
+  };
+  if (!tp->calc_Tsfc) {                // "initialize for safety" (:946-967): the history albedos are not touched
+    forget_sw();
+    CICE_HIP(hipMemsetAsync(dc(0), 0, 4 * nc * 8, s));
+    fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
+    fan_->fork(s);
+    for (int k = 0; k < 4; ++k) CICE_HIP(hipMemcpyAsync(alb[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
+    down_sw();
+    fan_->join();
+    CICE_HIP(hipStreamSynchronize(s));
+    keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+    return;
+  }
+  CICE_REQUIRE(f->swvdr && f->swvdf && f->swidr && f->swidf && f->coszen, "cice_step_radiation_dedd: NULL forcing");
+  CICE_REQUIRE(!dp->tr_pond || (f->apondn && f->hpondn), "cice_step_radiation_dedd: tr_pond needs apondn and hpondn");
+  forget_sw();
+  fan_->fork(s);
+  if (!resident) {                     // of the state the scheme reads these four; the rest of the batch's state is stale now
+    therm2_state_ = false;
+    aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
+    tracer_copy(tp->nt_Tsfc - 1, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
+  }
+  const double* in2[D_2D] = {f->coszen, f->swvdr, f->swvdf, f->swidr, f->swidf};
+  for (int k = 0; k < D_2D; ++k) CICE_HIP(hipMemcpyAsync(d2(k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  if (dp->tr_pond) {
+    CICE_HIP(hipMemcpyAsync(dc(7), f->apondn, nc * 8, hipMemcpyHostToDevice, cs()));
+    CICE_HIP(hipMemcpyAsync(dc(8), f->hpondn, nc * 8, hipMemcpyHostToDevice, cs()));
+  }
+  fan_->join();
+  DeddArgs a{};
+  a.p = *dp;
+  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.tsfc_planes = NTRCR; a.snow_given = 0;
+  a.blk = blk_.p;
+  a.aicen = aicen_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.Tsfc = trcrn_.p + (size_t)(tp->nt_Tsfc - 1) * np;
+  a.coszen = d2(D_COSZEN); a.swvdr = d2(D_SWVDR); a.swvdf = d2(D_SWVDF); a.swidr = d2(D_SWIDR); a.swidf = d2(D_SWIDF);
+  if (dp->tr_pond) { a.fp = dc(7); a.hp = dc(8); }
+  a.alvdrn = dc(0); a.alidrn = dc(1); a.alvdfn = dc(2); a.alidfn = dc(3); a.albicen = dc(4); a.albsnon = dc(5); a.albpndn = dc(6);
+  a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Iswabsn = Iswabs_.p; a.Sswabsn = Sswabs_.p;
+  const bool timed = dedd_timed_;
+  for (int k = 0; k < 2 && timed; ++k)
+    if (!dedd_ev_[k]) CICE_HIP(hipEventCreate(&dedd_ev_[k]));
+  if (timed) CICE_HIP(hipEventRecord(dedd_ev_[0], s));
+  dedd_launch(a, s);
+  if (timed) CICE_HIP(hipEventRecord(dedd_ev_[1], s));
+  fan_->fork(s);
+  double* const out7[7] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon, f->albpndn};
+  for (int k = 0; k < 7; ++k) CICE_HIP(hipMemcpyAsync(out7[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
+  down_sw();
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  if (timed) CICE_HIP(hipEventElapsedTime(&dedd_ms_, dedd_ev_[0], dedd_ev_[1]));
+  keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+}
+
+void ColumnBatch::dedd_times(bool enable, float ms[1]) {
+  dedd_timed_ = enable;
+  if (ms) ms[0] = dedd_ms_;
 }
 
 void ColumnBatch::radiation_chain(int mode) {

@@ -21,6 +21,7 @@
 #include "itd.h"
 #include "ridge.h"
 #include "shortwave.h"
+#include "dedd.h"
 #include "transport.h"
 #include "batch.h"
 
@@ -130,6 +131,12 @@ struct cice_ctx {
   bool have_sw = false;
   DevBuf<double> sw_d;
   DevBuf<int32_t> sw_i;
+  // delta-Eddington shortwave (dedd.h): what cice_shortwave_dedd_init was given and derived; staging and list of the
+  // block-wise entry.  Independent of sp / have_sw: a context may hold both schemes
+  DeddParams dp{};
+  bool have_dedd = false;
+  DevBuf<double> dedd_d;
+  DevBuf<int32_t> dedd_i;
   // device is required lazily: domain queries work on a CPU-only host
   // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
   // process may have changed the current device since the last call (another context on another GPU,

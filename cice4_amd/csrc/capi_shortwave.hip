@@ -9,7 +9,8 @@ int cice_shortwave_init(cice_ctx* ctx, const cice_shortwave_config* cfg) {
   CICE_REQUIRE(c_->have_thermo, "cice_shortwave_init: cice_thermo_init has not been called");
   CICE_REQUIRE(cfg->shortwave == 0 || cfg->shortwave == 1, "cice_shortwave_init: shortwave must be 0 (default) or 1 (dEdd)");
   if (cfg->shortwave == 1)
-    throw Error{CICE_EUNSUPPORTED, "cice_shortwave_init: shortwave = 'dEdd' (delta-Eddington) is not built"};
+    throw Error{CICE_EUNSUPPORTED, "cice_shortwave_init: shortwave = 'dEdd' (delta-Eddington) has an entry of its own, "
+                                   "cice_shortwave_dedd_init"};
   if (!c_->tp.heat_capacity)
     throw Error{CICE_EUNSUPPORTED, "cice_shortwave_init: heat_capacity = F (absorbed_solar's nilyr = 1 branch) is not built"};
   CICE_REQUIRE(cfg->albedo_type == 0 || cfg->albedo_type == 1, "cice_shortwave_init: albedo_type must be 0 (default) or 1 (constant)");

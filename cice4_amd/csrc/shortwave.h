@@ -1,6 +1,6 @@
 // Shortwave radiation, shortwave = 'default' (ccsm3), on the device: shortwave_ccsm3 with compute_albedos, constant_albedos
 // and absorbed_solar (source/ice_shortwave.F90:364-1185) as one kernel, and the scaling of prep_radiation
-// (source/ice_step_mod.F90:84-218) as another.  Delta-Eddington is not built.
+// (source/ice_step_mod.F90:84-218) as another.  Delta-Eddington: dedd.h.
 //
 // Arithmetic: the reference's operations in the reference's order, uncontracted (the Makefile's -ffp-contract=off).  exp is
 // the restated glibc exp of libm_exact.h, one call per ice layer with the reference's argument expression

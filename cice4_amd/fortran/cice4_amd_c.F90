@@ -684,6 +684,49 @@ module cice4_amd_c
       end function
    end interface
 
+   ! shortwave radiation, shortwave = 'dEdd' (source/ice_shortwave.F90: shortwave_dEdd; cice4_amd/csrc/dedd.hip) and the dEdd
+   ! branch of step_radiation (source/ice_step_mod.F90:872-916)
+   type, bind(C) :: cice_dedd_config
+      real(c_double) :: R_ice, R_pnd, R_snw
+      real(c_double) :: awtvdr, awtidr, awtvdf, awtidf
+      integer(c_int) :: tr_pond
+   end type
+
+   type, bind(C) :: cice_radiation_dedd_fields
+      integer(c_int) :: ncat, state_resident
+      type(c_ptr) :: aicen, trcrn, vicen, vsnon
+      type(c_ptr) :: swvdr, swvdf, swidr, swidf
+      type(c_ptr) :: coszen
+      type(c_ptr) :: apondn, hpondn
+      type(c_ptr) :: alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, albpndn, fswsfcn, fswintn, fswthrun
+      type(c_ptr) :: Sswabsn, Iswabsn
+   end type
+
+   interface
+      integer(c_int) function cice_shortwave_dedd_init(ctx, cfg) bind(C, name='cice_shortwave_dedd_init')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_dedd_config), intent(in) :: cfg
+      end function
+      integer(c_int) function cice_shortwave_dEdd(ctx, nx_block, ny_block, icells, indxi, indxj, coszen, aice, vice, vsno, &
+            fs, rhosnw, rsnw, fp, hp, swvdr, swvdf, swidr, swidf, alvdr, alvdf, alidr, alidf, fswsfc, fswint, fswthru, &
+            Sswabs, Iswabs, albice, albsno, albpnd) bind(C, name='cice_shortwave_dEdd')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, icells
+         integer(c_int), intent(in) :: indxi(*), indxj(*)
+         real(c_double), intent(in) :: coszen(*), aice(*), vice(*), vsno(*), fs(*), rhosnw(*), rsnw(*), fp(*), hp(*), &
+                                       swvdr(*), swvdf(*), swidr(*), swidf(*)
+         real(c_double), intent(out) :: alvdr(*), alvdf(*), alidr(*), alidf(*), fswsfc(*), fswint(*), fswthru(*), &
+                                        Sswabs(*), Iswabs(*), albice(*), albsno(*), albpnd(*)
+      end function
+      integer(c_int) function cice_step_radiation_dedd(ctx, f) bind(C, name='cice_step_radiation_dedd')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_radiation_dedd_fields), intent(in) :: f
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

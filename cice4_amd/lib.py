@@ -144,6 +144,21 @@ class RadiationFields(C.Structure):
         (n, C.c_void_p) for n in RADIATION_STATE + RADIATION_IN + RADIATION_OUT + ("coszen",)]
 
 
+class DeddConfig(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("R_ice", "R_pnd", "R_snw", "awtvdr", "awtidr", "awtvdf", "awtidf")] + [
+        ("tr_pond", C.c_int)]
+
+
+RADIATION_DEDD_IN = ("swvdr", "swvdf", "swidr", "swidf", "coszen", "apondn", "hpondn")
+RADIATION_DEDD_OUT = ("alvdrn", "alidrn", "alvdfn", "alidfn", "albicen", "albsnon", "albpndn", "fswsfcn", "fswintn", "fswthrun",
+                      "Sswabsn", "Iswabsn")
+
+
+class RadiationDeddFields(C.Structure):
+    _fields_ = [("ncat", C.c_int), ("state_resident", C.c_int)] + [
+        (n, C.c_void_p) for n in RADIATION_STATE + RADIATION_DEDD_IN + RADIATION_DEDD_OUT]
+
+
 class PrepRadiationFields(C.Structure):
     _fields_ = [("ncat", C.c_int), ("sw_resident", C.c_int)] + [(n, C.c_void_p) for n in PREP_RADIATION_PTRS]
 
@@ -1031,6 +1046,41 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(self.lib.cice_radiation_times(self.h, int(enable), ms))
         return tuple(ms)
+
+    # ---- shortwave radiation, shortwave = 'dEdd' (ice_shortwave: shortwave_dEdd) --------------
+    DEDD_IN = ("coszen", "aice", "vice", "vsno", "fs", "rhosnw", "rsnw", "fp", "hp", "swvdr", "swvdf", "swidr", "swidf")
+    DEDD_OUT = ("alvdr", "alvdf", "alidr", "alidf", "fswsfc", "fswint", "fswthru", "Sswabs", "Iswabs", "albice", "albsno",
+                "albpnd")
+
+    def shortwave_dedd_init(self, R_ice=0.0, R_pnd=0.0, R_snw=0.0, awtvdr=0.00318, awtidr=0.00182, awtvdf=0.63282,
+                            awtidf=0.36218, tr_pond=False):
+        """cice_shortwave_dedd_init (after thermo_init).  The defaults are the reference's namelist defaults and the
+        weights of ice_constants.  Independent of shortwave_init: a context may hold both schemes."""
+        cfg = DeddConfig(R_ice, R_pnd, R_snw, awtvdr, awtidr, awtvdf, awtidf, int(tr_pond))
+        self._ck(self.lib.cice_shortwave_dedd_init(self.h, C.byref(cfg)))
+
+    def shortwave_dEdd(self, icells, indxi, indxj, a):
+        """cice_shortwave_dEdd on one block and category.  a: the arrays of DEDD_IN ((ny,nx); rhosnw, rsnw (nslyr,ny,nx))
+        in; the arrays of DEDD_OUT ((ny,nx), Sswabs (nslyr,ny,nx), Iswabs (nilyr,ny,nx)) are written on the whole block."""
+        ny, nx = a["aice"].shape
+        self._ck(self.lib.cice_shortwave_dEdd(self.h, nx, ny, icells, _i4(indxi), _i4(indxj),
+                                              *[_f8(a[k]) for k in self.DEDD_IN], *[_f8(a[k]) for k in self.DEDD_OUT]))
+
+    def step_radiation_dedd(self, a, state_resident=False):
+        """cice_step_radiation_dedd on the batch (thermo_batch_alloc).  a: swvdr, swvdf, swidr, swidf, coszen (nb,ny,nx),
+        the arrays of RADIATION_DEDD_OUT, under tr_pond apondn and hpondn, and -- unless state_resident -- aicen, trcrn,
+        vicen, vsnon."""
+        f = RadiationDeddFields()
+        f.ncat, f.state_resident = NCAT, int(state_resident)
+        for n, _t in RadiationDeddFields._fields_[2:]:
+            setattr(f, n, _f8(a[n]) if a.get(n) is not None else None)
+        self._ck(self.lib.cice_step_radiation_dedd(self.h, C.byref(f)))
+
+    def dedd_times(self, enable=True):
+        """cice_dedd_times: switch the event timing on / off; the device time (ms) of the last timed k_shortwave_dedd"""
+        ms = (C.c_float * 1)()
+        self._ck(self.lib.cice_dedd_times(self.h, int(enable), ms))
+        return ms[0]
 
     def therm2_itd_times(self, enable=True):
         """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""

@@ -766,6 +766,53 @@ int cice_radiation_chain(cice_ctx *ctx, int mode);
  * k_shortwave_ccsm3 and k_prep_radiation. */
 int cice_radiation_times(cice_ctx *ctx, int enable, float ms[2]);
 
+/* ---- shortwave radiation, shortwave = 'dEdd' (delta-Eddington; source/ice_shortwave.F90:1197-3681: shortwave_dEdd with
+ * compute_dEdd and solution_dEdd, shortwave_dEdd_set_snow, shortwave_dEdd_set_pond; the dEdd branch of step_radiation,
+ * source/ice_step_mod.F90:872-916) on the device ----
+ * cice_shortwave_dedd_init: the namelist's tuning values R_ice, R_pnd, R_snw (0 = untuned), the weights awt* of
+ * ice_constants for the history albedos, and tr_pond (1: pond fraction and depth are the caller's apondn, hpondn; 0: set
+ * diagnostically by shortwave_dEdd_set_pond).  The tuned ice optical properties (compute_dEdd :2357-2423) and
+ * exp_min = exp(-10) are computed here, once, on the host.  An entry of its own beside cice_shortwave_init: a context may
+ * hold both schemes, and neither call changes what the other's entries do.  heat_capacity, calc_Tsfc and nt_Tsfc are those
+ * of cice_thermo_init: CICE_EINVAL without that call, CICE_EUNSUPPORTED with heat_capacity = 0. */
+typedef struct {
+  double R_ice, R_pnd, R_snw;
+  double awtvdr, awtidr, awtvdf, awtidf;
+  int tr_pond;
+} cice_dedd_config;
+int cice_shortwave_dedd_init(cice_ctx *ctx, const cice_dedd_config *cfg);
+/* Drop-in for `call shortwave_dEdd(...)`: one block, one category, host pointers, the reference's argument order; all
+ * arrays (nx_block,ny_block), rhosnw, rsnw, Sswabs (nx_block,ny_block,nslyr), Iswabs (nx_block,ny_block,nilyr).  fs,
+ * rhosnw, rsnw, fp, hp are inputs (what shortwave_dEdd_set_snow / _set_pond or the pond tracers gave the caller).  Every
+ * output is written on the whole block: zero off the list and where coszen <= puny, the four albedos included.  exp is
+ * glibc's restated, sqrt and division are correctly rounded: the outputs are meant to agree bit for bit. */
+int cice_shortwave_dEdd(cice_ctx *ctx, int nx_block, int ny_block, int icells, const int32_t *indxi, const int32_t *indxj,
+                        const double *coszen, const double *aice, const double *vice, const double *vsno, const double *fs,
+                        const double *rhosnw, const double *rsnw, const double *fp, const double *hp, const double *swvdr,
+                        const double *swvdf, const double *swidr, const double *swidf, double *alvdr, double *alvdf,
+                        double *alidr, double *alidf, double *fswsfc, double *fswint, double *fswthru, double *Sswabs,
+                        double *Iswabs, double *albice, double *albsno, double *albpnd);
+/* step_radiation with shortwave = 'dEdd' as ONE call on the batch, all blocks and categories; the list of a (category,
+ * block) is aicen > puny on the block's physical cells.  The fields of cice_radiation_fields without ocn_albedo, plus:
+ * coszen (nx,ny,nb), an INPUT (compute_coszen and the orbital code stay on the host, once per block); albpndn
+ * (nx,ny,ncat,nb), an output; apondn, hpondn (nx,ny,ncat,nb), read under tr_pond only, where NULL is CICE_EINVAL.
+ * state_resident means what it means for cice_step_radiation.  The results stay in the batch's shortwave buffers as after
+ * cice_step_radiation: cice_prep_radiation's sw_resident and cice_radiation_chain work behind this call unchanged.
+ * calc_Tsfc = 0: the four albedos, fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn are zero-filled; albicen, albsnon and
+ * albpndn are left alone, as in the reference. */
+typedef struct {
+  int ncat, state_resident;
+  const double *aicen, *trcrn, *vicen, *vsnon;
+  const double *swvdr, *swvdf, *swidr, *swidf;
+  const double *coszen;
+  const double *apondn, *hpondn;
+  double *alvdrn, *alidrn, *alvdfn, *alidfn, *albicen, *albsnon, *albpndn, *fswsfcn, *fswintn, *fswthrun;
+  double *Sswabsn, *Iswabsn;
+} cice_radiation_dedd_fields;
+int cice_step_radiation_dedd(cice_ctx *ctx, const cice_radiation_dedd_fields *f);
+/* Measurement aid (scripts/dedd_cost.py), off by default: ms[0] the device time (ms) of the last timed k_shortwave_dedd. */
+int cice_dedd_times(cice_ctx *ctx, int enable, float ms[1]);
+
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
  * dependencies from ntrcr / trcr_depend (ice_init.F90:848-852: 0 area tracer, 1 ice-volume, 2 snow-volume tracer),
