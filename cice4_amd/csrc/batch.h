@@ -71,6 +71,33 @@ inline long long status_count(const unsigned long long* h) {
 // "no stop": what every entry with the reference's l_stop / istop / jstop reports first
 inline void clear_stop(int32_t* l_stop, int32_t* istop, int32_t* jstop) { *l_stop = 0; *istop = 0; *jstop = 0; }
 
+// The device times of a stage: N intervals between N + 1 events on one stream.  While it is off nothing is created and
+// nothing recorded; the events are made at the first timed use and go with the clock.
+template <int N>
+struct StageClock {
+  hipEvent_t ev[N + 1] = {};
+  bool on = false;
+  float ms[N] = {};
+  StageClock() = default;
+  StageClock(const StageClock&) = delete;
+  StageClock& operator=(const StageClock&) = delete;
+  ~StageClock() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void mark(int k, hipStream_t s) {    // event k on the stream, if on
+    if (on && !ev[k]) CICE_HIP(hipEventCreate(&ev[k]));
+    if (on) CICE_HIP(hipEventRecord(ev[k], s));
+  }
+  void read(int a, int b) {            // the intervals [a, b), once the stream has passed their events
+    for (int k = a; k < b && on; ++k) CICE_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+  }
+  void query(bool enable, float* out) {   // a *_times entry: the flag, and the times of the last timed call
+    on = enable;
+    for (int k = 0; k < N && out; ++k) out[k] = ms[k];
+  }
+};
+
 // the error key of a thermo launch as the reference's stop: the cell (of the list, or of the dense plane), category, block
 void decode_err(unsigned long long key, int nx, int ncat, const int32_t* indxi, const int32_t* indxj, int32_t* l_stop,
                 int32_t* istop, int32_t* jstop, int32_t* nstop, int32_t* bstop);
@@ -113,12 +140,15 @@ class ColumnBatch {
   void prep_radiation(const ThermoParams* tp, const cice_prep_radiation_fields* f);
   // step_radiation for shortwave = 'dEdd' (dedd.h); dp: the parameters of cice_shortwave_dedd_init
   void step_radiation_dedd(const ThermoParams* tp, const DeddParams* dp, const cice_radiation_dedd_fields* f);
-  void dedd_times(bool enable, float ms[1]);        // the last timed k_shortwave_dedd
+  void dedd_times(bool enable, float ms[1]) { dedd_clock_.query(enable, ms); }   // the last timed k_shortwave_dedd
   void radiation_chain(int mode);                   // cice_radiation_chain
-  void radiation_times(bool enable, float ms[2]);   // the last timed k_shortwave_ccsm3, k_prep_radiation
+  void radiation_times(bool enable, float ms[2]) {  // the last timed k_shortwave_ccsm3, k_prep_radiation
+    sw_clock_.query(enable, ms);
+    prep_clock_.query(enable, ms ? ms + 1 : nullptr);
+  }
   void handover_time(bool enable, float* ms);       // the last timed k_state_from_transport (0: none since enabled)
   void set_option(const char* key, int value);      // before or after alloc; kept across re-allocations
-  void itd_times(bool enable, float ms[4]);         // likewise
+  void itd_times(bool enable, float ms[4]) { itd_clock_.query(enable, ms); }     // likewise
   void cleanup_times(bool enable, float ms[CLEAN_TIMES]);
   // "thermo_niter", one byte per (cell, category); "thermo_perm", the permutation of the last sorted step as int32 -- either
   // packed in 8-byte words.  Returns their number, -1 for another name.
@@ -132,12 +162,22 @@ class ColumnBatch {
   std::vector<Field> fields(const cice_thermo_fields* h);
   hipStream_t cs() { return fan_->forked ? fan_->next() : stream_; }   // the stream for the next host <-> device copy
   void tracer_copy(int it, const double* from, double* to, hipMemcpyKind kind);
+  // The caller's state arrays, and their copies to (hipMemcpyHostToDevice) or from the batch in the order they travel: the
+  // named members, then the tracer planes t0 .. t1 - 1.  A download writes through the pointers (the state of every entry
+  // that downloads is its non-const members).
+  enum { ST_AICEN = 1, ST_VICEN = 2, ST_VSNON = 4, ST_EICEN = 8, ST_ESNON = 16, ST_ALL = 31 };
+  struct HostState { const double *aicen, *vicen, *vsnon, *eicen, *esnon, *trcrn; };
+  void move_state(const HostState& h, int members, int t0, int t1, hipMemcpyKind kind);
+  // the caller's fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn, and their copies to or from the five shortwave buffers
+  struct SwArrays { double* h[5]; };
+  void move_sw(const SwArrays& h, hipMemcpyKind kind);
+  void zero_sw(hipStream_t s);
   // with_sw = false: the five shortwave arrays stay behind (cice_radiation_chain: the device copies are the host's)
   void upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef,
                      bool with_sw = true);
   void download_fields(const ThermoParams* tp, cice_thermo_fields* h);
   void launch_step(const ThermoParams& tp, double dt, double yday, unsigned long long status[THERMO_STATUS_WORDS],
-                   float* elapsed_ms, hipEvent_t* ev);
+                   StageClock<1>& clock);
   enum { MRG_UP = 1, MRG_RUN = 2, MRG_DOWN = 4, MRG_ALL = 7 };
   void merge_phases(const cice_merge_fields* f, const double* aicen_init_dev, bool atmo_on_device, int phases);
   void read_rec(unsigned long long h[ITD_REC_WORDS]);
@@ -165,13 +205,11 @@ class ColumnBatch {
   int sort_chunk_ = 0, sort_group_ = 8;      // chunk 0: no sorting (k_thermo_dense) -- the default: DESIGN.md 3.3
   DevBuf<unsigned char> niter_;              // solver iterations of every (cell, category) in the last step
   bool kept_aicen_init_ = false;             // mrg_in_ holds the concentrations step_therm1 found (step_therm2_itd)
-  // thickness-distribution stage: its extra fields, record words, the events of itd_times
+  // thickness-distribution stage: its extra fields, record words, the clock of itd_times
   DevBuf<double> itd_b_;
   DevBuf<int32_t> itd_bi_;
   DevBuf<unsigned long long> rec_;
-  hipEvent_t itd_ev_[5] = {};
-  bool itd_timed_ = false;
-  float itd_ms_[4] = {0, 0, 0, 0};
+  StageClock<4> itd_clock_;
   // cleanup stage: the state is what step_therm2_itd left (all ntrcr tracer planes); its 2-d fields, tmask, block words
   bool therm2_state_ = false;
   DevBuf<double> clean_b_, clean_t_;
@@ -196,15 +234,33 @@ class ColumnBatch {
   int rad_mode_ = 0;
   const double* sw_host_[5] = {};
   void forget_sw() { sw_resident_ = false; sw_armed_ = false; }
-  void keep_sw(const double* fswsfc, const double* fswint, const double* fswthrun, const double* Sswabs, const double* Iswabs);
-  hipEvent_t rad_ev_[4] = {};
-  bool rad_timed_ = false;
-  float rad_ms_[2] = {0, 0};
+  void keep_sw(const SwArrays& h);
+  // What the two schemes of step_radiation differ in.  buf: the scheme's buffer, planes2 (nx, ny, nb) planes -- the 2-d
+  // inputs in2[k] in plane k -- then planesc (nx, ny, ncat, nb) planes: the nout per-category outputs, behind them apondn
+  // and hpondn where `pond` says they are read.
+  struct RadScheme {
+    const char* entry;                       // the C entry, in front of every error text
+    int state_resident;
+    HostState state;
+    DevBuf<double>* buf;
+    int planes2, planesc;
+    struct { const double* h; bool may_be_null; } in2[5];
+    bool pond;
+    const double* pondn[2];
+    int nout;
+    double* out[7];
+    SwArrays sw;
+    StageClock<1>* clock;
+    bool forget_first;                       // the record of the shortwave buffers ends before the forcing is looked at
+    double* coszen_out;                      // filled with 0.5 on the host afterwards, or nullptr
+  };
+  // launch(p2, pc): the scheme's kernel on the buffer's 2-d planes p2 and per-category planes pc
+  template <class Launch> void radiation_stage(const ThermoParams& tp, const RadScheme& r, Launch launch);
+  template <class Args> void radiation_args(Args& a, const ThermoParams& tp, double* p2, int sw, double* pc);
+  StageClock<1> sw_clock_, prep_clock_;      // k_shortwave_ccsm3, k_prep_radiation: the two times of radiation_times
   // delta-Eddington: coszen and the four sw fields, the seven albedo outputs, apondn and hpondn
   DevBuf<double> dedd_b_;
-  hipEvent_t dedd_ev_[2] = {};
-  bool dedd_timed_ = false;
-  float dedd_ms_ = 0.0f;
+  StageClock<1> dedd_clock_;
   hipEvent_t ho_ev_[2] = {};                 // around k_state_from_transport (handover_time)
   bool ho_timed_ = false, ho_pending_ = false;
   float ho_ms_ = 0.0f;

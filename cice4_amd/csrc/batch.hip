@@ -39,17 +39,11 @@ unsigned long long itd_shift_key(const unsigned long long* r, int N) {
 }
 
 ColumnBatch::~ColumnBatch() {
-  for (hipEvent_t e : itd_ev_)
-    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : clean_ev_)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ridge_ev_)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ho_ev_)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : rad_ev_)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : dedd_ev_)
     if (e) (void)hipEventDestroy(e);
 }
 
@@ -115,6 +109,30 @@ void ColumnBatch::tracer_copy(int it, const double* from, double* to, hipMemcpyK
   CICE_HIP(hipMemcpy2DAsync(to + o, pitch, from + o, pitch, np * 8, (size_t)NCAT * nb_, kind, cs()));
 }
 
+void ColumnBatch::move_state(const HostState& h, int members, int t0, int t1, hipMemcpyKind kind) {
+  const bool up = kind == hipMemcpyHostToDevice;
+  const size_t bytes = (size_t)nx_ * ny_ * nb_ * 8;
+  const struct { int member; const double* h; double* d; size_t per; } arr[5] = {
+      {ST_AICEN, h.aicen, aicen_.p, NCAT}, {ST_VICEN, h.vicen, vicen_.p, NCAT}, {ST_VSNON, h.vsnon, vsnon_.p, NCAT},
+      {ST_EICEN, h.eicen, eicen_.p, NCAT * NILYR}, {ST_ESNON, h.esnon, esnon_.p, NCAT * NSLYR}};
+  for (const auto& x : arr)
+    if (members & x.member)
+      CICE_HIP(hipMemcpyAsync(up ? x.d : const_cast<double*>(x.h), up ? x.h : x.d, bytes * x.per, kind, cs()));
+  for (int it = t0; it < t1; ++it)
+    tracer_copy(it, up ? h.trcrn : trcrn_.p, up ? trcrn_.p : const_cast<double*>(h.trcrn), kind);
+}
+
+void ColumnBatch::move_sw(const SwArrays& h, hipMemcpyKind kind) {
+  DevBuf<double>* const d[5] = {&fswsfc_, &fswint_, &fswthrun_, &Sswabs_, &Iswabs_};
+  for (int k = 0; k < 5; ++k)
+    if (kind == hipMemcpyHostToDevice) d[k]->upload(h.h[k], cs());
+    else d[k]->download(h.h[k], cs());
+}
+
+void ColumnBatch::zero_sw(hipStream_t s) {
+  fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
+}
+
 void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields* h, bool with_fbot_tbot, bool with_coef,
                                 bool with_sw) {
   const size_t n2 = (size_t)nx_ * ny_ * nb_;
@@ -150,9 +168,9 @@ void ColumnBatch::upload(const ThermoParams* tp, const cice_thermo_fields* h) {
 }
 
 // launches the dense kernel; the status words (error key, update counters) land in `status` once the
-// stream has been synchronised
+// stream has been synchronised, and the clock holds the kernel's events
 void ColumnBatch::launch_step(const ThermoParams& tp, double dt, double yday, unsigned long long status[THERMO_STATUS_WORDS],
-                              float* elapsed_ms, hipEvent_t* ev) {
+                              StageClock<1>& clock) {
   hipStream_t s = stream_;
   const size_t n2 = (size_t)nx_ * ny_ * nb_, nc = n2 * NCAT;
   thermo_status_reset(key_.p, s);
@@ -168,11 +186,7 @@ void ColumnBatch::launch_step(const ThermoParams& tp, double dt, double yday, un
     niter_.zero(s);
   }
   a.niter = niter_.p;
-  if (elapsed_ms) {
-    CICE_HIP(hipEventCreate(&ev[0]));
-    CICE_HIP(hipEventCreate(&ev[1]));
-    CICE_HIP(hipEventRecord(ev[0], s));
-  }
+  clock.mark(0, s);
   static const int env_chunk = [] { const char* e = std::getenv("CICE4_AMD_THERMO_SORT"); return e ? std::atoi(e) : -1; }();
   const int chunk = env_chunk >= 0 ? env_chunk : sort_chunk_;
   static const int env_group = [] { const char* e = std::getenv("CICE4_AMD_THERMO_GROUP"); return e ? std::atoi(e) : -1; }();
@@ -187,7 +201,7 @@ void ColumnBatch::launch_step(const ThermoParams& tp, double dt, double yday, un
   } else {
     thermo_launch_dense(a, s);
   }
-  if (elapsed_ms) CICE_HIP(hipEventRecord(ev[1], s));
+  clock.mark(1, s);
   CICE_HIP(hipMemcpyAsync(status, key_.p, THERMO_STATUS_WORDS * 8, hipMemcpyDeviceToHost, s));
 }
 
@@ -209,14 +223,12 @@ void ColumnBatch::step(const ThermoParams* tp, double dt, double yday, long long
   therm2_state_ = false;
   forget_sw();                         // the column update writes the shortwave buffers
   unsigned long long h[THERMO_STATUS_WORDS];
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  launch_step(*tp, dt, yday, h, elapsed_ms, ev);
+  StageClock<1> clock;                 // of this call: no events without elapsed_ms
+  clock.on = elapsed_ms != nullptr;
+  launch_step(*tp, dt, yday, h, clock);
   CICE_HIP(hipStreamSynchronize(stream_));
-  if (elapsed_ms) {
-    CICE_HIP(hipEventElapsedTime(elapsed_ms, ev[0], ev[1]));
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-  }
+  clock.read(0, 1);
+  if (elapsed_ms) *elapsed_ms = clock.ms[0];
   if (n_updates) *n_updates = status_count(h);
   decode_err(h[0], nx_, NCAT, nullptr, nullptr, l_stop, istop, jstop, nstop, bstop);
 }
@@ -343,7 +355,8 @@ void ColumnBatch::step_therm1(const ThermoParams* tp, double chio, double dt, do
   CICE_HIP(hipMemcpyAsync(mrg_in_.p, aicen_.p, nc * 8, hipMemcpyDeviceToDevice, s));
   kept_aicen_init_ = true;
   unsigned long long h[THERMO_STATUS_WORDS];
-  launch_step(*tp, dt, yday, h, nullptr, nullptr);
+  StageClock<1> untimed;
+  launch_step(*tp, dt, yday, h, untimed);
   merge_phases(mg, mrg_in_.p, atm != nullptr, MRG_RUN);
   fan_->fork(s);   // ... and every download after the last kernel
   merge_phases(mg, mrg_in_.p, atm != nullptr, MRG_DOWN);
@@ -391,22 +404,16 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
   if (itd_b_.n < 2 * nc + 12 * n2) itd_b_.alloc(2 * nc + 12 * n2);
   if (itd_bi_.n < n2 + (size_t)nb_) itd_bi_.alloc(n2 + (size_t)nb_);
   rec_.alloc(ITD_REC_WORDS);
-  const bool timed = itd_timed_;
-  for (hipEvent_t& e : itd_ev_)
-    if (timed && !e) CICE_HIP(hipEventCreate(&e));
   double* ainit = itd_b_.p;
   double* vinit = itd_b_.p + nc;
   double* d2 = itd_b_.p + 2 * nc;
   int32_t* flag = itd_bi_.p + n2;
   const int ntr = ip->ntrcr, it_T = ip->it_Tsfc;
-  auto upload = [&](bool state) {
+  const HostState hs{f->aicen, f->vicen, f->vsnon, f->eicen, f->esnon, f->trcrn};
+  auto upload = [&](bool state) {      // (a resident state: the tracer planes but the surface temperature's)
     fan_->fork(s);
-    if (state) {
-      aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
-      eicen_.upload(f->eicen, cs()); esnon_.upload(f->esnon, cs());
-    }
-    for (int it = 0; it < ntr; ++it)
-      if (state || it != it_T) tracer_copy(it, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
+    move_state(hs, state ? ST_ALL : 0, 0, state ? ntr : it_T, hipMemcpyHostToDevice);
+    if (!state) move_state(hs, 0, it_T + 1, ntr, hipMemcpyHostToDevice);
     if (f->aicen_init) CICE_HIP(hipMemcpyAsync(ainit, f->aicen_init, nc * 8, hipMemcpyHostToDevice, cs()));
     CICE_HIP(hipMemcpyAsync(vinit, f->vicen_init, nc * 8, hipMemcpyHostToDevice, cs()));
     const double* in2[12] = {f->aice, f->aice0, f->frain, f->frzmlt, f->Tf, f->rside, f->fresh, f->fsalt, f->fhocn,
@@ -434,23 +441,23 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
   auto run = [&](int bfail, int nlimit, int bend_add, int bend_melt) {
     ItdArgs k = a;
     k.bfail = bfail; k.nlimit = nlimit;
-    if (timed) CICE_HIP(hipEventRecord(itd_ev_[0], s));
+    itd_clock_.mark(0, s);
     itd_launch_rain_aggregate(k, s);
-    if (timed) CICE_HIP(hipEventRecord(itd_ev_[1], s));
+    itd_clock_.mark(1, s);
     if (k.kitd) itd_launch_linear(k, s);
-    if (timed) CICE_HIP(hipEventRecord(itd_ev_[2], s));
+    itd_clock_.mark(2, s);
     k.bend = bend_add;
     itd_launch_add_new_ice(k, s);
-    if (timed) CICE_HIP(hipEventRecord(itd_ev_[3], s));
+    itd_clock_.mark(3, s);
     k.bend = bend_melt;
     itd_launch_lateral_melt(k, s);
-    if (timed) CICE_HIP(hipEventRecord(itd_ev_[4], s));
+    itd_clock_.mark(4, s);
   };
   unsigned long long r[ITD_REC_WORDS];
   upload(!resident);
   run(nb_, 0, nb_, nb_);
   read_rec(r);
-  for (int k = 0; k < 4 && timed; ++k) CICE_HIP(hipEventElapsedTime(&itd_ms_[k], itd_ev_[k], itd_ev_[k + 1]));
+  itd_clock_.read(0, 4);
   clear_stop(l_stop, istop, jstop);
   *bstop = 0; *stage = 0;
   int bl = -1, N = 0, ba = -1;
@@ -471,9 +478,7 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
     if (key) { *istop = (int32_t)((key - 1) % nx_) + 1; *jstop = (int32_t)((key - 1) / nx_) + 1; }
   }
   fan_->fork(s);
-  aicen_.download(f->aicen, cs()); vicen_.download(f->vicen, cs()); vsnon_.download(f->vsnon, cs());
-  eicen_.download(f->eicen, cs()); esnon_.download(f->esnon, cs());
-  for (int it = 0; it < ntr; ++it) tracer_copy(it, trcrn_.p, f->trcrn, hipMemcpyDeviceToHost);
+  move_state(hs, ST_ALL, 0, ntr, hipMemcpyDeviceToHost);
   double* out2[12] = {f->aice, f->aice0, nullptr, nullptr, nullptr, nullptr, f->fresh, f->fsalt, f->fhocn, f->frazil,
                       f->meltl, f->frz_onset};
   for (int k = 0; k < 12; ++k)
@@ -723,87 +728,102 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
   therm2_state_ = true;
 }
 
+void ColumnBatch::keep_sw(const SwArrays& h) {
+  sw_resident_ = true;
+  sw_armed_ = rad_mode_ == 1;
+  for (int k = 0; k < 5; ++k) sw_host_[k] = h.h[k];
+}
+
+// step_radiation (ice_step_mod.F90:764-973) on the batch with the scheme `r` describes: see include/cice4_amd.h
+template <class Launch>
+void ColumnBatch::radiation_stage(const ThermoParams& tp, const RadScheme& r, Launch launch) {
+  auto text = [&](const char* what) { return std::string(r.entry) + ": " + what; };
+  CICE_REQUIRE(r.state_resident == 0 || r.state_resident == 1, text("state_resident must be 0 or 1"));
+  const bool resident = r.state_resident == 1;
+  CICE_REQUIRE(!resident || therm2_state_,
+               text("state_resident needs a cice_step_ridge or cice_step_therm2_cleanup on this batch in front"));
+  CICE_REQUIRE(resident || (r.state.aicen && r.state.trcrn && r.state.vicen && r.state.vsnon), text("NULL state"));
+  bool outputs = true, forcing = true;
+  for (int k = 0; k < r.nout; ++k) outputs = outputs && r.out[k];
+  for (double* h : r.sw.h) outputs = outputs && h;
+  CICE_REQUIRE(outputs, text("NULL output"));
+  hipStream_t s = stream_;
+  if (r.forget_first) forget_sw();
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  if (r.buf->n != r.planes2 * n2 + r.planesc * nc) r.buf->alloc(r.planes2 * n2 + r.planesc * nc);
+  double* const p2 = r.buf->p;
+  double* const pc = p2 + r.planes2 * n2;
+  if (!tp.calc_Tsfc) {                 // "initialize for safety" (:946-967): the four albedos and the five; nothing else is touched
+    forget_sw();
+    CICE_HIP(hipMemsetAsync(pc, 0, 4 * nc * 8, s));
+    zero_sw(s);
+    fan_->fork(s);
+    for (int k = 0; k < 4; ++k) CICE_HIP(hipMemcpyAsync(r.out[k], pc + k * nc, nc * 8, hipMemcpyDeviceToHost, cs()));
+    move_sw(r.sw, hipMemcpyDeviceToHost);
+    fan_->join();
+    CICE_HIP(hipStreamSynchronize(s));
+    keep_sw(r.sw);
+    return;
+  }
+  for (const auto& x : r.in2) forcing = forcing && (x.h || x.may_be_null);
+  CICE_REQUIRE(forcing, text("NULL forcing"));
+  CICE_REQUIRE(!r.pond || (r.pondn[0] && r.pondn[1]), text("tr_pond needs apondn and hpondn"));
+  forget_sw();
+  fan_->fork(s);
+  if (!resident) {                     // of the state the scheme reads these four; the rest of the batch's state is stale now
+    therm2_state_ = false;
+    move_state(r.state, ST_AICEN | ST_VICEN | ST_VSNON, tp.nt_Tsfc - 1, tp.nt_Tsfc, hipMemcpyHostToDevice);
+  }
+  for (int k = 0; k < 5; ++k)
+    if (r.in2[k].h) CICE_HIP(hipMemcpyAsync(p2 + k * n2, r.in2[k].h, n2 * 8, hipMemcpyHostToDevice, cs()));
+  for (int k = 0; k < 2 && r.pond; ++k)
+    CICE_HIP(hipMemcpyAsync(pc + (r.nout + k) * nc, r.pondn[k], nc * 8, hipMemcpyHostToDevice, cs()));
+  fan_->join();
+  r.clock->mark(0, s);
+  launch(p2, pc);
+  r.clock->mark(1, s);
+  fan_->fork(s);
+  for (int k = 0; k < r.nout; ++k) CICE_HIP(hipMemcpyAsync(r.out[k], pc + k * nc, nc * 8, hipMemcpyDeviceToHost, cs()));
+  move_sw(r.sw, hipMemcpyDeviceToHost);
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  r.clock->read(0, 1);
+  for (size_t q = 0; q < n2 && r.coszen_out; ++q) r.coszen_out[q] = K::p5;   // "sun above the horizon" (:843), every cell
+  keep_sw(r.sw);
+}
+
+// what ShortwaveArgs and DeddArgs have in common: the batch's state and shortwave buffers, the four shortwave fields from
+// plane `sw` of p2 on, the six albedo outputs they share at the head of pc
+template <class Args>
+void ColumnBatch::radiation_args(Args& a, const ThermoParams& tp, double* p2, int sw, double* pc) {
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.tsfc_planes = NTRCR;
+  a.blk = blk_.p;
+  a.aicen = aicen_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.Tsfc = trcrn_.p + (size_t)(tp.nt_Tsfc - 1) * np;
+  a.swvdr = p2 + sw * n2; a.swvdf = p2 + (sw + 1) * n2; a.swidr = p2 + (sw + 2) * n2; a.swidf = p2 + (sw + 3) * n2;
+  a.alvdrn = pc; a.alidrn = pc + nc; a.alvdfn = pc + 2 * nc; a.alidfn = pc + 3 * nc; a.albicen = pc + 4 * nc; a.albsnon = pc + 5 * nc;
+  a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Iswabsn = Iswabs_.p; a.Sswabsn = Sswabs_.p;
+}
+
 // planes of rad_b_: the 2-d fields (nx, ny, nb each), then six (nx, ny, ncat, nb) arrays -- step_radiation's albedo outputs;
 // prep_radiation keeps its copy of aicen in the first of them
 enum { R_SWVDR = 0, R_SWVDF, R_SWIDR, R_SWIDF, R_OCN, R_GBM, R_AICE = R_GBM + 4, R_SF, R_FAC, R_2D };
 
-void ColumnBatch::keep_sw(const double* fswsfc, const double* fswint, const double* fswthrun, const double* Sswabs,
-                          const double* Iswabs) {
-  sw_resident_ = true;
-  sw_armed_ = rad_mode_ == 1;
-  const double* h[5] = {fswsfc, fswint, fswthrun, Sswabs, Iswabs};
-  for (int k = 0; k < 5; ++k) sw_host_[k] = h[k];
-}
-
-// step_radiation (ice_step_mod.F90:764-973) for shortwave = 'default' on the batch: see include/cice4_amd.h
+// shortwave = 'default': coszen is an output, 0.5 everywhere
 void ColumnBatch::step_radiation(const ThermoParams* tp, const ShortwaveParams* sp, const cice_radiation_fields* f) {
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
   CICE_REQUIRE(sp, "cice_shortwave_init has not been called");
-  CICE_REQUIRE(f->state_resident == 0 || f->state_resident == 1, "cice_step_radiation: state_resident must be 0 or 1");
-  const bool resident = f->state_resident == 1;
-  CICE_REQUIRE(!resident || therm2_state_,
-               "cice_step_radiation: state_resident needs a cice_step_ridge or cice_step_therm2_cleanup on this batch in front");
-  CICE_REQUIRE(resident || (f->aicen && f->trcrn && f->vicen && f->vsnon), "cice_step_radiation: NULL state");
-  CICE_REQUIRE(f->alvdrn && f->alidrn && f->alvdfn && f->alidfn && f->albicen && f->albsnon && f->fswsfcn && f->fswintn &&
-                   f->fswthrun && f->Sswabsn && f->Iswabsn, "cice_step_radiation: NULL output");
-  hipStream_t s = stream_;
-  forget_sw();
-  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
-  if (rad_b_.n != R_2D * n2 + 6 * nc) rad_b_.alloc(R_2D * n2 + 6 * nc);
-  auto d2 = [&](int k) { return rad_b_.p + (size_t)k * n2; };
-  auto dc = [&](int k) { return rad_b_.p + R_2D * n2 + (size_t)k * nc; };
-  double* const alb[4] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn};
-  auto down_sw = [&] {
-    fswsfc_.download(f->fswsfcn, cs()); fswint_.download(f->fswintn, cs()); fswthrun_.download(f->fswthrun, cs());
-    Sswabs_.download(f->Sswabsn, cs()); Iswabs_.download(f->Iswabsn, cs());
-  };
-  if (!tp->calc_Tsfc) {                // "initialize for safety" (:946-967): albicen, albsnon, coszen are not touched
-    CICE_HIP(hipMemsetAsync(dc(0), 0, 4 * nc * 8, s));
-    fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
-    fan_->fork(s);
-    for (int k = 0; k < 4; ++k) CICE_HIP(hipMemcpyAsync(alb[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
-    down_sw();
-    fan_->join();
-    CICE_HIP(hipStreamSynchronize(s));
-    keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
-    return;
-  }
-  CICE_REQUIRE(f->swvdr && f->swvdf && f->swidr && f->swidf, "cice_step_radiation: NULL forcing");
-  fan_->fork(s);
-  if (!resident) {                     // of the state the scheme reads these four; the rest of the batch's state is stale now
-    therm2_state_ = false;
-    aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
-    tracer_copy(tp->nt_Tsfc - 1, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
-  }
-  const double* in2[5] = {f->swvdr, f->swvdf, f->swidr, f->swidf, f->ocn_albedo};
-  for (int k = 0; k < 5; ++k)
-    if (in2[k]) CICE_HIP(hipMemcpyAsync(d2(R_SWVDR + k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
-  fan_->join();
-  ShortwaveArgs a{};
-  a.p = *sp;
-  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.tsfc_planes = NTRCR;
-  a.blk = blk_.p;
-  a.aicen = aicen_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.Tsfc = trcrn_.p + (size_t)(tp->nt_Tsfc - 1) * np;
-  a.swvdr = d2(R_SWVDR); a.swvdf = d2(R_SWVDF); a.swidr = d2(R_SWIDR); a.swidf = d2(R_SWIDF);
-  a.ocn_albedo = f->ocn_albedo ? d2(R_OCN) : nullptr;
-  a.alvdrn = dc(0); a.alidrn = dc(1); a.alvdfn = dc(2); a.alidfn = dc(3); a.albicen = dc(4); a.albsnon = dc(5);
-  a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Iswabsn = Iswabs_.p; a.Sswabsn = Sswabs_.p;
-  const bool timed = rad_timed_;
-  for (int k = 0; k < 2 && timed; ++k)
-    if (!rad_ev_[k]) CICE_HIP(hipEventCreate(&rad_ev_[k]));
-  if (timed) CICE_HIP(hipEventRecord(rad_ev_[0], s));
-  shortwave_launch(a, s);
-  if (timed) CICE_HIP(hipEventRecord(rad_ev_[1], s));
-  fan_->fork(s);
-  double* const out6[6] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon};
-  for (int k = 0; k < 6; ++k) CICE_HIP(hipMemcpyAsync(out6[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
-  down_sw();
-  fan_->join();
-  CICE_HIP(hipStreamSynchronize(s));
-  if (timed) CICE_HIP(hipEventElapsedTime(&rad_ms_[0], rad_ev_[0], rad_ev_[1]));
-  if (f->coszen)                       // "sun above the horizon" (:843), every cell of every block
-    for (size_t q = 0; q < n2; ++q) f->coszen[q] = K::p5;
-  keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+  const RadScheme r{"cice_step_radiation", f->state_resident, {f->aicen, f->vicen, f->vsnon, nullptr, nullptr, f->trcrn},
+                    &rad_b_, R_2D, 6, {{f->swvdr}, {f->swvdf}, {f->swidr}, {f->swidf}, {f->ocn_albedo, true}}, false, {}, 6,
+                    {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon},
+                    {{f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn}}, &sw_clock_, true, f->coszen};
+  radiation_stage(*tp, r, [&](double* p2, double* pc) {
+    ShortwaveArgs a{};
+    a.p = *sp;
+    radiation_args(a, *tp, p2, R_SWVDR, pc);
+    a.ocn_albedo = f->ocn_albedo ? p2 + R_OCN * ((size_t)nx_ * ny_ * nb_) : nullptr;
+    shortwave_launch(a, stream_);
+  });
 }
 
 // prep_radiation (ice_step_mod.F90:84-218) on the batch: see include/cice4_amd.h
@@ -820,17 +840,14 @@ void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiati
   if (rad_b_.n != R_2D * n2 + 6 * nc) rad_b_.alloc(R_2D * n2 + 6 * nc);
   auto d2 = [&](int k) { return rad_b_.p + (size_t)k * n2; };
   double* const daicen = rad_b_.p + R_2D * n2;
-  auto down_sw = [&] {
-    fswsfc_.download(f->fswsfcn, cs()); fswint_.download(f->fswintn, cs()); fswthrun_.download(f->fswthrun, cs());
-    Sswabs_.download(f->Sswabsn, cs()); Iswabs_.download(f->Iswabsn, cs());
-  };
+  const SwArrays sw{{f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn}};
   if (!tp->calc_Tsfc) {                // "initialize for safety" (:195-212)
-    fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
+    zero_sw(s);
     fan_->fork(s);
-    down_sw();
+    move_sw(sw, hipMemcpyDeviceToHost);
     fan_->join();
     CICE_HIP(hipStreamSynchronize(s));
-    keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+    keep_sw(sw);
     return;
   }
   CICE_REQUIRE(f->swvdr && f->swvdf && f->swidr && f->swidf && f->alvdr_gbm && f->alvdf_gbm && f->alidr_gbm &&
@@ -844,10 +861,7 @@ void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiati
   CICE_HIP(hipMemcpyAsync(d2(R_SF), f->scale_factor, n2 * 8, hipMemcpyHostToDevice, cs()));
   CICE_HIP(hipMemcpyAsync(d2(R_FAC), f->fswfac, n2 * 8, hipMemcpyHostToDevice, cs()));   // (kept off the physical cells)
   CICE_HIP(hipMemcpyAsync(daicen, f->aicen, nc * 8, hipMemcpyHostToDevice, cs()));
-  if (!resident) {
-    fswsfc_.upload(f->fswsfcn, cs()); fswint_.upload(f->fswintn, cs()); fswthrun_.upload(f->fswthrun, cs());
-    Sswabs_.upload(f->Sswabsn, cs()); Iswabs_.upload(f->Iswabsn, cs());
-  }
+  if (!resident) move_sw(sw, hipMemcpyHostToDevice);
   fan_->join();
   PrepRadiationArgs a{};
   a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.blk = blk_.p;
@@ -855,114 +869,49 @@ void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiati
   a.alvdr_gbm = d2(R_GBM); a.alvdf_gbm = d2(R_GBM + 1); a.alidr_gbm = d2(R_GBM + 2); a.alidf_gbm = d2(R_GBM + 3);
   a.aice = d2(R_AICE); a.aicen = daicen; a.scale_factor = d2(R_SF); a.fswfac = d2(R_FAC);
   a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Sswabsn = Sswabs_.p; a.Iswabsn = Iswabs_.p;
-  const bool timed = rad_timed_;
-  for (int k = 2; k < 4 && timed; ++k)
-    if (!rad_ev_[k]) CICE_HIP(hipEventCreate(&rad_ev_[k]));
-  if (timed) CICE_HIP(hipEventRecord(rad_ev_[2], s));
+  prep_clock_.mark(0, s);
   prep_radiation_launch(a, s);
-  if (timed) CICE_HIP(hipEventRecord(rad_ev_[3], s));
+  prep_clock_.mark(1, s);
   fan_->fork(s);
   CICE_HIP(hipMemcpyAsync(f->scale_factor, d2(R_SF), n2 * 8, hipMemcpyDeviceToHost, cs()));
   CICE_HIP(hipMemcpyAsync(f->fswfac, d2(R_FAC), n2 * 8, hipMemcpyDeviceToHost, cs()));
-  down_sw();
+  move_sw(sw, hipMemcpyDeviceToHost);
   fan_->join();
   CICE_HIP(hipStreamSynchronize(s));
-  if (timed) CICE_HIP(hipEventElapsedTime(&rad_ms_[1], rad_ev_[2], rad_ev_[3]));
-  keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
+  prep_clock_.read(0, 1);
+  keep_sw(sw);
 }
 
 // planes of dedd_b_: coszen and the four sw fields (nx, ny, nb each), then nine (nx, ny, ncat, nb) arrays -- the four
 // albedos, albicen, albsnon, albpndn, and the inputs apondn, hpondn
 enum { D_COSZEN = 0, D_SWVDR, D_SWVDF, D_SWIDR, D_SWIDF, D_2D };
 
-// step_radiation (ice_step_mod.F90:764-973) for shortwave = 'dEdd' on the batch: see include/cice4_amd.h
+// shortwave = 'dEdd': coszen is an input; a call refused for its forcing or its pond arrays leaves the record of the
+// shortwave buffers standing
 void ColumnBatch::step_radiation_dedd(const ThermoParams* tp, const DeddParams* dp, const cice_radiation_dedd_fields* f) {
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
   CICE_REQUIRE(dp, "cice_shortwave_dedd_init has not been called");
-  CICE_REQUIRE(f->state_resident == 0 || f->state_resident == 1, "cice_step_radiation_dedd: state_resident must be 0 or 1");
-  const bool resident = f->state_resident == 1;
-  CICE_REQUIRE(!resident || therm2_state_,
-               "cice_step_radiation_dedd: state_resident needs a cice_step_ridge or cice_step_therm2_cleanup on this batch in front");
-  CICE_REQUIRE(resident || (f->aicen && f->trcrn && f->vicen && f->vsnon), "cice_step_radiation_dedd: NULL state");
-  CICE_REQUIRE(f->alvdrn && f->alidrn && f->alvdfn && f->alidfn && f->albicen && f->albsnon && f->albpndn && f->fswsfcn &&
-                   f->fswintn && f->fswthrun && f->Sswabsn && f->Iswabsn, "cice_step_radiation_dedd: NULL output");
-  hipStream_t s = stream_;
-  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
-  if (dedd_b_.n != D_2D * n2 + 9 * nc) dedd_b_.alloc(D_2D * n2 + 9 * nc);
-  auto d2 = [&](int k) { return dedd_b_.p + (size_t)k * n2; };
-  auto dc = [&](int k) { return dedd_b_.p + D_2D * n2 + (size_t)k * nc; };
-  double* const alb[4] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn};
-  auto down_sw = [&] {
-    fswsfc_.download(f->fswsfcn, cs()); fswint_.download(f->fswintn, cs()); fswthrun_.download(f->fswthrun, cs());
-    Sswabs_.download(f->Sswabsn, cs()); Iswabs_.download(f->Iswabsn, cs());
-  };
-  if (!tp->calc_Tsfc) {                // "initialize for safety" (:946-967): the history albedos are not touched
-    forget_sw();
-    CICE_HIP(hipMemsetAsync(dc(0), 0, 4 * nc * 8, s));
-    fswsfc_.zero(s); fswint_.zero(s); fswthrun_.zero(s); Sswabs_.zero(s); Iswabs_.zero(s);
-    fan_->fork(s);
-    for (int k = 0; k < 4; ++k) CICE_HIP(hipMemcpyAsync(alb[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
-    down_sw();
-    fan_->join();
-    CICE_HIP(hipStreamSynchronize(s));
-    keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
-    return;
-  }
-  CICE_REQUIRE(f->swvdr && f->swvdf && f->swidr && f->swidf && f->coszen, "cice_step_radiation_dedd: NULL forcing");
-  CICE_REQUIRE(!dp->tr_pond || (f->apondn && f->hpondn), "cice_step_radiation_dedd: tr_pond needs apondn and hpondn");
-  forget_sw();
-  fan_->fork(s);
-  if (!resident) {                     // of the state the scheme reads these four; the rest of the batch's state is stale now
-    therm2_state_ = false;
-    aicen_.upload(f->aicen, cs()); vicen_.upload(f->vicen, cs()); vsnon_.upload(f->vsnon, cs());
-    tracer_copy(tp->nt_Tsfc - 1, f->trcrn, trcrn_.p, hipMemcpyHostToDevice);
-  }
-  const double* in2[D_2D] = {f->coszen, f->swvdr, f->swvdf, f->swidr, f->swidf};
-  for (int k = 0; k < D_2D; ++k) CICE_HIP(hipMemcpyAsync(d2(k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
-  if (dp->tr_pond) {
-    CICE_HIP(hipMemcpyAsync(dc(7), f->apondn, nc * 8, hipMemcpyHostToDevice, cs()));
-    CICE_HIP(hipMemcpyAsync(dc(8), f->hpondn, nc * 8, hipMemcpyHostToDevice, cs()));
-  }
-  fan_->join();
-  DeddArgs a{};
-  a.p = *dp;
-  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.tsfc_planes = NTRCR; a.snow_given = 0;
-  a.blk = blk_.p;
-  a.aicen = aicen_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p; a.Tsfc = trcrn_.p + (size_t)(tp->nt_Tsfc - 1) * np;
-  a.coszen = d2(D_COSZEN); a.swvdr = d2(D_SWVDR); a.swvdf = d2(D_SWVDF); a.swidr = d2(D_SWIDR); a.swidf = d2(D_SWIDF);
-  if (dp->tr_pond) { a.fp = dc(7); a.hp = dc(8); }
-  a.alvdrn = dc(0); a.alidrn = dc(1); a.alvdfn = dc(2); a.alidfn = dc(3); a.albicen = dc(4); a.albsnon = dc(5); a.albpndn = dc(6);
-  a.fswsfcn = fswsfc_.p; a.fswintn = fswint_.p; a.fswthrun = fswthrun_.p; a.Iswabsn = Iswabs_.p; a.Sswabsn = Sswabs_.p;
-  const bool timed = dedd_timed_;
-  for (int k = 0; k < 2 && timed; ++k)
-    if (!dedd_ev_[k]) CICE_HIP(hipEventCreate(&dedd_ev_[k]));
-  if (timed) CICE_HIP(hipEventRecord(dedd_ev_[0], s));
-  dedd_launch(a, s);
-  if (timed) CICE_HIP(hipEventRecord(dedd_ev_[1], s));
-  fan_->fork(s);
-  double* const out7[7] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon, f->albpndn};
-  for (int k = 0; k < 7; ++k) CICE_HIP(hipMemcpyAsync(out7[k], dc(k), nc * 8, hipMemcpyDeviceToHost, cs()));
-  down_sw();
-  fan_->join();
-  CICE_HIP(hipStreamSynchronize(s));
-  if (timed) CICE_HIP(hipEventElapsedTime(&dedd_ms_, dedd_ev_[0], dedd_ev_[1]));
-  keep_sw(f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn);
-}
-
-void ColumnBatch::dedd_times(bool enable, float ms[1]) {
-  dedd_timed_ = enable;
-  if (ms) ms[0] = dedd_ms_;
+  const RadScheme r{"cice_step_radiation_dedd", f->state_resident, {f->aicen, f->vicen, f->vsnon, nullptr, nullptr, f->trcrn},
+                    &dedd_b_, D_2D, 9, {{f->coszen}, {f->swvdr}, {f->swvdf}, {f->swidr}, {f->swidf}}, dp->tr_pond != 0,
+                    {f->apondn, f->hpondn}, 7, {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon, f->albpndn},
+                    {{f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn}}, &dedd_clock_, false, nullptr};
+  radiation_stage(*tp, r, [&](double* p2, double* pc) {
+    const size_t nc = (size_t)nx_ * ny_ * nb_ * NCAT;
+    DeddArgs a{};
+    a.p = *dp;
+    radiation_args(a, *tp, p2, D_SWVDR, pc);
+    a.snow_given = 0;
+    a.coszen = p2;
+    a.albpndn = pc + 6 * nc;
+    if (dp->tr_pond) { a.fp = pc + 7 * nc; a.hp = pc + 8 * nc; }
+    dedd_launch(a, stream_);
+  });
 }
 
 void ColumnBatch::radiation_chain(int mode) {
   CICE_REQUIRE(mode == 0 || mode == 1, "cice_radiation_chain: mode must be 0 or 1");
   rad_mode_ = mode;
   sw_armed_ = false;
-}
-
-void ColumnBatch::radiation_times(bool enable, float ms[2]) {
-  rad_timed_ = enable;
-  for (int k = 0; k < 2 && ms; ++k) ms[k] = rad_ms_[k];
 }
 
 void ColumnBatch::handover_time(bool enable, float* ms) {
@@ -983,11 +932,6 @@ void ColumnBatch::ridge_times(bool enable, float ms[RIDGE_TIMES]) {
 void ColumnBatch::cleanup_times(bool enable, float ms[CLEAN_TIMES]) {
   clean_timed_ = enable;
   for (int k = 0; k < CLEAN_TIMES && ms; ++k) ms[k] = clean_ms_[k];
-}
-
-void ColumnBatch::itd_times(bool enable, float ms[4]) {
-  itd_timed_ = enable;
-  for (int k = 0; k < 4 && ms; ++k) ms[k] = itd_ms_[k];
 }
 
 long long ColumnBatch::debug_read(const char* what, long long* out, long long cap) const {

@@ -181,6 +181,22 @@ struct cice_ctx {
   }                                                           \
   return CICE_OK;
 
+// The list (icells, indxi, indxj) of a block-wise entry on its (nx, ny) block as one int32 per cell: 1 on the listed cells,
+// 0 elsewhere -- or, with `positions`, the cell's place in the list counted from 1, where no cell may be named twice.
+inline std::vector<int32_t> list_mask(int nx, int ny, int icells, const int32_t* indxi, const int32_t* indxj,
+                                      bool positions = false) {
+  CICE_REQUIRE(nx >= 1 && ny >= 1 && icells >= 0 && (size_t)icells <= (size_t)nx * ny && (icells == 0 || (indxi && indxj)),
+               "bad dimensions or NULL index list");
+  std::vector<int32_t> m((size_t)nx * ny, 0);
+  for (int ij = 0; ij < icells; ++ij) {
+    CICE_REQUIRE(indxi[ij] >= 1 && indxi[ij] <= nx && indxj[ij] >= 1 && indxj[ij] <= ny, "index list outside the block");
+    int32_t& w = m[(size_t)(indxj[ij] - 1) * nx + indxi[ij] - 1];
+    CICE_REQUIRE(!positions || w == 0, "index list names a cell twice");
+    w = positions ? ij + 1 : 1;
+  }
+  return m;
+}
+
 #define NEED_EVP CICE_REQUIRE(c_->evp != nullptr, "cice_evp_init has not been called")
 // (`also`: a pointer the entry has always checked in the same breath)
 #define NEED_BATCH(also) CICE_REQUIRE(c_->batch.allocated() && (also), "cice_thermo_batch_alloc has not been called")

@@ -35,14 +35,8 @@ int cice_shortwave_dEdd(cice_ctx* ctx, int nx, int ny, int icells, const int32_t
   CICE_REQUIRE(coszen && aice && vice && vsno && fs && rhosnw && rsnw && fp && hp && swvdr && swvdf && swidr && swidf && alvdr &&
                    alvdf && alidr && alidf && fswsfc && fswint && fswthru && Sswabs && Iswabs && albice && albsno && albpnd,
                "shortwave_dEdd: NULL argument");
-  CICE_REQUIRE(nx >= 1 && ny >= 1 && icells >= 0 && (size_t)icells <= (size_t)nx * ny && (icells == 0 || (indxi && indxj)),
-               "bad dimensions or NULL index list");
-  const size_t np = (size_t)nx * ny;
-  std::vector<int32_t> on(np, 0);
-  for (int ij = 0; ij < icells; ++ij) {
-    CICE_REQUIRE(indxi[ij] >= 1 && indxi[ij] <= nx && indxj[ij] >= 1 && indxj[ij] <= ny, "index list outside the block");
-    on[(size_t)(indxj[ij] - 1) * nx + indxi[ij] - 1] = 1;
-  }
+  const std::vector<int32_t> on = list_mask(nx, ny, icells, indxi, indxj);
+  const size_t np = on.size();
   c_->need_device();
   // planes of the staging buffer: the inputs in argument order (rhosnw, rsnw nslyr planes each), then the outputs
   enum { P_COSZEN = 0, P_AICE, P_VICE, P_VSNO, P_FS, P_RHOSNW, P_RSNW = P_RHOSNW + NSLYR, P_FP = P_RSNW + NSLYR, P_HP, P_SW,

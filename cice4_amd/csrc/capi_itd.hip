@@ -27,15 +27,7 @@ struct ItdBlock {   // one (nx, ny) block staged on the device
   ItdBlock(cice_ctx* c_, int nx, int ny, int icells, const int32_t* indxi_, const int32_t* indxj_)
       : c(c_), np((size_t)nx * ny), indxi(indxi_), indxj(indxj_) {
     CICE_REQUIRE(c->have_itd, "cice_itd_init has not been called");
-    CICE_REQUIRE(nx >= 1 && ny >= 1 && icells >= 0 && (size_t)icells <= np && (icells == 0 || (indxi && indxj)),
-                 "bad dimensions or NULL index list");
-    lp.assign(np, 0);
-    for (int ij = 0; ij < icells; ++ij) {
-      CICE_REQUIRE(indxi[ij] >= 1 && indxi[ij] <= nx && indxj[ij] >= 1 && indxj[ij] <= ny, "index list outside the block");
-      int32_t& w = lp[(size_t)(indxj[ij] - 1) * nx + indxi[ij] - 1];
-      CICE_REQUIRE(w == 0, "index list names a cell twice");
-      w = ij + 1;
-    }
+    lp = list_mask(nx, ny, icells, indxi, indxj, true);
     c->need_device();
     if (c->itd_d.n < IB_PLANES * np) c->itd_d.alloc(IB_PLANES * np);
     if (c->itd_i.n < 7 * np + 4) c->itd_i.alloc(7 * np + 4);

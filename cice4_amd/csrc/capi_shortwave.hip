@@ -38,14 +38,8 @@ int cice_shortwave_ccsm3(cice_ctx* ctx, int nx, int ny, int icells, const int32_
   CICE_REQUIRE(c_->have_sw, "cice_shortwave_init has not been called");
   CICE_REQUIRE(aicen && vicen && vsnon && Tsfcn && swvdr && swvdf && swidr && swidf && alvdrn && alidrn && alvdfn && alidfn &&
                    fswsfc && fswint && fswthru && Iswabs && albin && albsn, "shortwave_ccsm3: NULL argument");
-  CICE_REQUIRE(nx >= 1 && ny >= 1 && icells >= 0 && (size_t)icells <= (size_t)nx * ny && (icells == 0 || (indxi && indxj)),
-               "bad dimensions or NULL index list");
-  const size_t np = (size_t)nx * ny;
-  std::vector<int32_t> on(np, 0);
-  for (int ij = 0; ij < icells; ++ij) {
-    CICE_REQUIRE(indxi[ij] >= 1 && indxi[ij] <= nx && indxj[ij] >= 1 && indxj[ij] <= ny, "index list outside the block");
-    on[(size_t)(indxj[ij] - 1) * nx + indxi[ij] - 1] = 1;
-  }
+  const std::vector<int32_t> on = list_mask(nx, ny, icells, indxi, indxj);
+  const size_t np = on.size();
   c_->need_device();
   // planes of the staging buffer: the nine inputs, the nine outputs, Iswabs
   enum { P_IN = 0, P_OCN = 8, P_OUT = 9, P_ISW = 18, P_PLANES = P_ISW + NILYR };

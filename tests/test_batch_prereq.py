@@ -49,6 +49,13 @@ def test_batch_entries_before_alloc(fresh):
 def test_settings_and_debug_reads_work_before_alloc(fresh):
     c = fresh
     assert len(c.therm2_itd_times(True)) == 4
+    # the six stage clocks: no device, no batch, nothing timed yet -- zeros, with the flag set and with it cleared again
+    for read, n in ((c.therm2_itd_times, 4), (c.therm2_cleanup_times, 12), (c.ridge_times, 41), (c.radiation_times, 2),
+                    (c.dedd_times, 1), (c.ridge_chain_time, 1)):
+        for enable in (True, False):
+            t = read(enable)
+            t = list(t.values()) if isinstance(t, dict) else list(t) if isinstance(t, tuple) else [t]
+            assert t == [0.0] * n, (read.__name__, enable, t)
     c.thermo_set_option("sort_chunk", 256)
     c.thermo_set_option("sort_group", 8)
     _refused(lambda: c.thermo_set_option("sort_chunk", 100), -1, "sort_chunk must be 0 or 256 .. 2048 in steps of 256")
