@@ -1,10 +1,12 @@
-// atmo_boundary_layer (source/ice_atmo.F90:56-384) for gfx950.  One lane = one (cell[, category]); the five
-// stability iterations (:264-305) run in registers.  exp is glibc's (libm_exact.h); log and atan are the device
-// library's (<= 1 ulp): the outputs agree with the reference's to ~1e-15 relative, not bit for bit -- which is why
-// the bit-exact whole-driver configuration keeps the reference's host routine.
+// atmo_boundary_layer (source/ice_atmo.F90:56-384) for gfx950.  One lane = one (cell[, category]); the cell routine
+// is atmo_cell.h's: the five stability iterations (:264-305) run in registers.  exp is glibc's (libm_exact.h); log
+// and atan are the device library's (<= 1 ulp): the outputs agree with the reference's to ~1e-15 relative, not bit
+// for bit -- which is why the bit-exact whole-driver configuration keeps the reference's host routine (DESIGN.md
+// section 3.6).
 #include <cmath>
 
 #include "atmo.h"
+#include "atmo_cell.h"
 
 namespace cice {
 
@@ -18,61 +20,6 @@ void AtmoParams::init() {
 }
 
 namespace {
-
-struct AtmoOut { double strx, stry, Tref, Qref, delt, delq, lhcoef, shcoef; };
-
-__device__ __forceinline__ double psimhu(double xd, double pih) {   // :165-166
-  return log((1.0 + xd * (2.0 + xd)) * (1.0 + xd * xd) / 8.0) - 2.0 * atan(xd) + pih;
-}
-__device__ __forceinline__ double psixhu(double xd) {               // :169
-  return 2.0 * log((1.0 + xd * xd) / 2.0);
-}
-
-__device__ __forceinline__ AtmoOut atmo_cell(const AtmoParams& P, int ocn, double Tsf, double potT, double uatm,
-                                             double vatm, double wind, double zlvl, double Qa, double rhoa) {
-  AtmoOut o;
-  const double vmag = fmax(P.umin, wind);                                             // :201 / :214
-  const double rdn = ocn ? sqrt(0.0027 / vmag + .000142 + .0000764 * vmag) : P.rdn_ice;  // :202 / :215
-  const double TsfK = Tsf + P.Tffresh;                                                // :232
-  const double qsat = P.qqq[ocn] * exp_libm(-P.TTT[ocn] / TsfK);
-  const double ssq = qsat / rhoa;
-  const double thva = potT * (1.0 + P.zvir * Qa);
-  const double delt = potT - TsfK, delq = Qa - ssq;
-  const double alz = log(zlvl / P.zref);
-  const double cp = P.cp_air * (1.0 + P.cpvir * ssq);
-  const double rhn = rdn, ren = rdn;                                                  // :248-249
-  double ustar = rdn * vmag, tstar = rhn * delt, qstar = ren * delq;
-  double hol = 0.0, stable = 0.0, psixh = 0.0, rd = 0.0, rh = 0.0, re = 0.0;
-  for (int k = 0; k < 5; ++k) {                                                        // :264
-    hol = P.vonkar * P.gravit * zlvl * (tstar / thva + qstar / (1.0 / P.zvir + Qa)) / (ustar * ustar);
-    hol = copysign(fmin(fabs(hol), 10.0), hol);
-    stable = 0.5 + copysign(0.5, hol);
-    double xqq = fmax(sqrt(fabs(1.0 - 16.0 * hol)), 1.0);
-    xqq = sqrt(xqq);
-    const double psimhs = -(0.7 * hol + 0.75 * (hol - 14.3) * exp_libm(-0.35 * hol) + 10.7);   // Jordan et al 1999
-    const double psimh = psimhs * stable + (1.0 - stable) * psimhu(xqq, P.pih);
-    psixh = psimhs * stable + (1.0 - stable) * psixhu(xqq);
-    rd = rdn / (1.0 + rdn / P.vonkar * (alz - psimh));                                 // :291-293
-    rh = rhn / (1.0 + rhn / P.vonkar * (alz - psixh));
-    re = ren / (1.0 + ren / P.vonkar * (alz - psixh));
-    ustar = rd * vmag; tstar = rh * delt; qstar = re * delq;
-  }
-  const double tau = rhoa * ustar * rd;                                               // :335
-  o.strx = tau * uatm; o.stry = tau * vatm;
-  o.shcoef = rhoa * ustar * cp * rh + 1.0;                                            // :359-360
-  o.lhcoef = rhoa * ustar * P.Lheat[ocn] * re;
-  hol = hol * P.zTrf / zlvl;                                                          // :365
-  double xqq = fmax(1.0, sqrt(fabs(1.0 - 16.0 * hol)));
-  xqq = sqrt(xqq);
-  const double psix2 = -5.0 * hol * stable + (1.0 - stable) * psixhu(xqq);
-  double fac = (rh / P.vonkar) * (alz + P.al2 - psixh + psix2);
-  o.Tref = potT - delt * fac;
-  o.Tref = o.Tref - 0.01 * P.zTrf;
-  fac = (re / P.vonkar) * (alz + P.al2 - psixh + psix2);
-  o.Qref = Qa - delq * fac;
-  o.delt = delt; o.delq = delq;
-  return o;
-}
 
 // one block, the reference's list: everything is zeroed first (:179-188, :313-318), then the listed cells
 __global__ __launch_bounds__(256) void k_atmo_zero(AtmoArgs a) {

@@ -7,6 +7,7 @@
 
 #include "atmo.h"
 #include "cleanup.h"
+#include "coupling.h"
 #include "dedd.h"
 #include "common.h"
 #include "domain.h"
@@ -141,6 +142,10 @@ class ColumnBatch {
   // step_radiation for shortwave = 'dEdd' (dedd.h); dp: the parameters of cice_shortwave_dedd_init
   void step_radiation_dedd(const ThermoParams* tp, const DeddParams* dp, const cice_radiation_dedd_fields* f);
   void dedd_times(bool enable, float ms[1]) { dedd_clock_.query(enable, ms); }   // the last timed k_shortwave_dedd
+  // coupling_prep (coupling.h); cp: the parameters of cice_coupling_init; halo: the context's ghost-cell update (bound = 1)
+  // or nullptr
+  void coupling_prep(const CouplingParams* cp, double dt, const cice_coupling_fields* f, Halo* halo);
+  void coupling_times(bool enable, float ms[2]) { cpl_clock_.query(enable, ms); }   // k_ocean_mixed_layer, k_coupling_prep
   void radiation_chain(int mode);                   // cice_radiation_chain
   void radiation_times(bool enable, float ms[2]) {  // the last timed k_shortwave_ccsm3, k_prep_radiation
     sw_clock_.query(enable, ms);
@@ -261,6 +266,13 @@ class ColumnBatch {
   // delta-Eddington: coszen and the four sw fields, the seven albedo outputs, apondn and hpondn
   DevBuf<double> dedd_b_;
   StageClock<1> dedd_clock_;
+  // coupling stage.  alb_scheme_: whose buffer holds the per-category albedos of the last successful step_radiation --
+  // ALB_CCSM3 rad_b_, ALB_DEDD dedd_b_, ALB_NONE neither: whatever rewrites or re-allocates those planes ends the record
+  enum { ALB_NONE = 0, ALB_CCSM3, ALB_DEDD };
+  int alb_scheme_ = ALB_NONE;
+  DevBuf<double> cpl_b_;                     // the 2-d fields, albcnt, and the uploaded per-category arrays
+  DevBuf<int32_t> cpl_bi_;                   // tmask
+  StageClock<2> cpl_clock_;
   hipEvent_t ho_ev_[2] = {};                 // around k_state_from_transport (handover_time)
   bool ho_timed_ = false, ho_pending_ = false;
   float ho_ms_ = 0.0f;

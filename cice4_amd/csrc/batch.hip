@@ -78,6 +78,7 @@ void ColumnBatch::alloc(hipStream_t stream, CopyFan& fan, int nx, int ny, int nb
   kept_aicen_init_ = false;
   therm2_state_ = false;
   forget_sw();
+  alb_scheme_ = ALB_NONE;
   const size_t np = (size_t)nx * ny, n2 = np * nb, nc = n2 * NCAT;
   std::vector<int32_t> hb;
   if (dom && same_layout(*dom)) {
@@ -749,6 +750,7 @@ void ColumnBatch::radiation_stage(const ThermoParams& tp, const RadScheme& r, La
   CICE_REQUIRE(outputs, text("NULL output"));
   hipStream_t s = stream_;
   if (r.forget_first) forget_sw();
+  alb_scheme_ = ALB_NONE;              // (a call that fails, or zero-fills, leaves no set of albedos to merge)
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
   if (r.buf->n != r.planes2 * n2 + r.planesc * nc) r.buf->alloc(r.planes2 * n2 + r.planesc * nc);
   double* const p2 = r.buf->p;
@@ -790,6 +792,7 @@ void ColumnBatch::radiation_stage(const ThermoParams& tp, const RadScheme& r, La
   r.clock->read(0, 1);
   for (size_t q = 0; q < n2 && r.coszen_out; ++q) r.coszen_out[q] = K::p5;   // "sun above the horizon" (:843), every cell
   keep_sw(r.sw);
+  alb_scheme_ = r.buf == &rad_b_ ? ALB_CCSM3 : ALB_DEDD;
 }
 
 // what ShortwaveArgs and DeddArgs have in common: the batch's state and shortwave buffers, the four shortwave fields from
@@ -836,6 +839,7 @@ void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiati
   CICE_REQUIRE(f->fswsfcn && f->fswintn && f->fswthrun && f->Sswabsn && f->Iswabsn, "cice_prep_radiation: NULL field");
   hipStream_t s = stream_;
   forget_sw();
+  if (alb_scheme_ == ALB_CCSM3) alb_scheme_ = ALB_NONE;   // (aicen is staged in the first albedo plane)
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
   if (rad_b_.n != R_2D * n2 + 6 * nc) rad_b_.alloc(R_2D * n2 + 6 * nc);
   auto d2 = [&](int k) { return rad_b_.p + (size_t)k * n2; };
@@ -912,6 +916,145 @@ void ColumnBatch::radiation_chain(int mode) {
   CICE_REQUIRE(mode == 0 || mode == 1, "cice_radiation_chain: mode must be 0 or 1");
   rad_mode_ = mode;
   sw_armed_ = false;
+}
+
+// planes of cpl_b_ (nx, ny, nb each): the nine inputs, the 13 in / out fields of scale_fluxes, the seven merged albedos, the
+// eight *_gbm, scale_factor; the mixed layer's eight inputs, sst, qdp, its 13 outputs and the four optional ones.  Behind
+// them albcnt (nstreams planes) and, where they are uploaded, the seven per-category albedos and aicen.
+enum { C_COSZEN = 0, C_AICE, C_TF, C_TAIR, C_QA, C_SWVDR, C_SWVDF, C_SWIDR, C_SWIDF, C_FLUX, C_ALB = C_FLUX + CPL_FLUXES,
+       C_GBM = C_ALB + 7, C_SF = C_GBM + 8, C_MIX_IN, C_SST = C_MIX_IN + 8, C_QDP, C_MIX_OUT, C_MIX_OPT = C_MIX_OUT + 13,
+       C_2D = C_MIX_OPT + 4 };
+
+// coupling_prep (drivers/cice4/CICE_RunMod.F90:588-767) on the batch: see include/cice4_amd.h
+void ColumnBatch::coupling_prep(const CouplingParams* cp, double dt, const cice_coupling_fields* f, Halo* halo) {
+  CICE_REQUIRE(cp, "cice_coupling_prep: cice_coupling_init has not been called");
+  CICE_REQUIRE(f->state_resident == 0 || f->state_resident == 1, "cice_coupling_prep: state_resident must be 0 or 1");
+  CICE_REQUIRE(f->alb_resident == 0 || f->alb_resident == 1, "cice_coupling_prep: alb_resident must be 0 or 1");
+  CICE_REQUIRE(f->nstreams >= 0, "cice_coupling_prep: nstreams must not be negative");
+  CICE_REQUIRE(!f->albcnt || f->nstreams >= 1, "cice_coupling_prep: albcnt is given with nstreams = 0");
+  const bool st_res = f->state_resident == 1, alb_res = f->alb_resident == 1, scale = cp->scale != 0, mixed = cp->mixed != 0;
+  CICE_REQUIRE(!st_res || therm2_state_,
+               "cice_coupling_prep: state_resident needs a cice_step_ridge or cice_step_therm2_cleanup on this batch in front");
+  CICE_REQUIRE(!alb_res || alb_scheme_ != ALB_NONE,
+               "cice_coupling_prep: alb_resident needs a cice_step_radiation or cice_step_radiation_dedd on this batch in front");
+  CICE_REQUIRE(!mixed || dt > 0.0, "cice_coupling_prep: dt must be positive");
+  // the host arrays by plane of cpl_b_
+  const double* in2[C_2D] = {};
+  double* out2[C_2D] = {};
+  const double* head[9] = {f->coszen, f->aice, f->Tf, f->Tair, f->Qa, f->swvdr, f->swvdf, f->swidr, f->swidf};
+  double* const flux[CPL_FLUXES] = {f->strairxT, f->strairyT, f->fsens, f->flat, f->fswabs, f->flwout, f->evap, f->Tref,
+                                    f->Qref, f->fresh, f->fsalt, f->fhocn, f->fswthru};
+  double* const res[16] = {f->alvdr, f->alidr, f->alvdf, f->alidf, f->albice, f->albsno, f->albpnd, f->alvdf_gbm,
+                           f->alidf_gbm, f->alvdr_gbm, f->alidr_gbm, f->fresh_gbm, f->fsalt_gbm, f->fhocn_gbm,
+                           f->fswthru_gbm, f->scale_factor};
+  static_assert(C_SF == C_ALB + 15 && C_MIX_IN == C_SF + 1, "order of res");
+  const double* mix_in[8] = {f->potT, f->uatm, f->vatm, f->wind, f->zlvl, f->rhoa, f->flw, f->hmix};
+  double* const mix_out[17] = {f->frzmlt, f->flwout_ocn, f->fsens_ocn, f->flat_ocn, f->evap_ocn, f->strairx_ocn, f->strairy_ocn,
+                               f->Tref_ocn, f->Qref_ocn, f->alvdr_ocn, f->alidr_ocn, f->alvdf_ocn, f->alidf_ocn, f->delt,
+                               f->delq, f->shcoef, f->lhcoef};
+  bool ok = true;
+  for (int k = 0; k < 9; ++k) {
+    const bool used = k == C_COSZEN || k >= C_SWVDR || scale || (mixed && k != C_TAIR);   // aice, Tf, Tair, Qa otherwise
+    ok = ok && (!used || head[k]);
+    if (used) in2[k] = head[k];
+  }
+  for (int k = 0; k < CPL_FLUXES; ++k) {
+    const bool used = scale || k >= CPL_FRESH;
+    ok = ok && (!used || flux[k]);
+    if (used) in2[C_FLUX + k] = flux[k];
+    if (scale) out2[C_FLUX + k] = flux[k];
+  }
+  for (int k = 0; k < 16; ++k) {
+    ok = ok && res[k];
+    out2[C_ALB + k] = res[k];
+  }
+  for (int k = 0; k < 8 && mixed; ++k) {
+    ok = ok && mix_in[k];
+    in2[C_MIX_IN + k] = mix_in[k];
+  }
+  for (int k = 0; k < 17 && mixed; ++k) {
+    ok = ok && (k >= 13 || mix_out[k]);
+    out2[C_MIX_OUT + k] = mix_out[k];
+  }
+  if (mixed) {
+    ok = ok && f->sst && f->qdp;
+    in2[C_SST] = out2[C_SST] = f->sst;
+    in2[C_QDP] = out2[C_QDP] = f->qdp;
+  }
+  ok = ok && (f->tmask || !(scale || mixed)) && (st_res || f->aicen);
+  ok = ok && (alb_res || (f->alvdrn && f->alidrn && f->alvdfn && f->alidfn && f->albicen && f->albsnon));
+  CICE_REQUIRE(ok, "cice_coupling_prep: NULL field");
+
+  hipStream_t s = stream_;
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  const size_t want = (C_2D + (size_t)f->nstreams) * n2 + 8 * nc;
+  if (cpl_b_.n != want) cpl_b_.alloc(want);
+  if (cpl_bi_.n != n2) cpl_bi_.alloc(n2);
+  auto d2 = [&](int k) { return cpl_b_.p + (size_t)k * n2; };
+  double* const dcnt = d2(C_2D);
+  double* const dc = dcnt + (size_t)f->nstreams * n2;      // alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, albpndn, aicen
+  fan_->fork(s);
+  if (f->tmask) CICE_HIP(hipMemcpyAsync(cpl_bi_.p, f->tmask, n2 * 4, hipMemcpyHostToDevice, cs()));
+  for (int k = 0; k < C_2D; ++k)
+    if (in2[k]) CICE_HIP(hipMemcpyAsync(d2(k), in2[k], n2 * 8, hipMemcpyHostToDevice, cs()));
+  if (f->albcnt) CICE_HIP(hipMemcpyAsync(dcnt, f->albcnt, (size_t)f->nstreams * n2 * 8, hipMemcpyHostToDevice, cs()));
+  const double* albn[7] = {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon, f->albpndn};
+  for (int k = 0; k < 7 && !alb_res; ++k)
+    if (albn[k]) CICE_HIP(hipMemcpyAsync(dc + k * nc, albn[k], nc * 8, hipMemcpyHostToDevice, cs()));
+  if (!st_res) CICE_HIP(hipMemcpyAsync(dc + 7 * nc, f->aicen, nc * 8, hipMemcpyHostToDevice, cs()));
+  fan_->join();
+
+  cpl_clock_.mark(0, s);
+  if (mixed) {                         // first: it reads fhocn, fswthru and aice before they are scaled
+    MixedLayerArgs m{};
+    m.p.init();
+    m.np = (int)np; m.nb = nb_; m.dt = dt; m.albocn = cp->albocn;
+    m.tmask = cpl_bi_.p;
+    m.potT = d2(C_MIX_IN); m.uatm = d2(C_MIX_IN + 1); m.vatm = d2(C_MIX_IN + 2); m.wind = d2(C_MIX_IN + 3);
+    m.zlvl = d2(C_MIX_IN + 4); m.rhoa = d2(C_MIX_IN + 5); m.flw = d2(C_MIX_IN + 6); m.hmix = d2(C_MIX_IN + 7);
+    m.Qa = d2(C_QA); m.Tf = d2(C_TF); m.aice = d2(C_AICE);
+    m.fhocn = d2(C_FLUX + CPL_FHOCN); m.fswthru = d2(C_FLUX + CPL_FSWTHRU);
+    m.swvdr = d2(C_SWVDR); m.swvdf = d2(C_SWVDF); m.swidr = d2(C_SWIDR); m.swidf = d2(C_SWIDF);
+    m.sst = d2(C_SST); m.qdp = d2(C_QDP);
+    double** const o[17] = {&m.frzmlt, &m.flwout_ocn, &m.fsens_ocn, &m.flat_ocn, &m.evap_ocn, &m.strairx_ocn, &m.strairy_ocn,
+                            &m.Tref_ocn, &m.Qref_ocn, &m.alvdr_ocn, &m.alidr_ocn, &m.alvdf_ocn, &m.alidf_ocn, &m.delt, &m.delq,
+                            &m.shcoef, &m.lhcoef};
+    for (int k = 0; k < 17; ++k) *o[k] = k < 13 || mix_out[k] ? d2(C_MIX_OUT + k) : nullptr;
+    ocean_mixed_layer_launch(m, s);
+  }
+  cpl_clock_.mark(1, s);
+  CouplingArgs a{};
+  a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.nstreams = f->nstreams; a.scale = scale;
+  a.tmask = f->tmask ? cpl_bi_.p : nullptr;
+  if (alb_res) {                       // the scheme's per-category outputs (radiation_args): albpndn is delta-Eddington's
+    const bool dedd = alb_scheme_ == ALB_DEDD;
+    const double* pc = dedd ? dedd_b_.p + D_2D * n2 : rad_b_.p + R_2D * n2;
+    a.alvdrn = pc; a.alidrn = pc + nc; a.alvdfn = pc + 2 * nc; a.alidfn = pc + 3 * nc; a.albicen = pc + 4 * nc;
+    a.albsnon = pc + 5 * nc; a.albpndn = dedd ? pc + 6 * nc : nullptr;
+  } else {
+    a.alvdrn = dc; a.alidrn = dc + nc; a.alvdfn = dc + 2 * nc; a.alidfn = dc + 3 * nc; a.albicen = dc + 4 * nc;
+    a.albsnon = dc + 5 * nc; a.albpndn = f->albpndn ? dc + 6 * nc : nullptr;
+  }
+  a.aicen = st_res ? aicen_.p : dc + 7 * nc;
+  a.coszen = d2(C_COSZEN); a.aice = d2(C_AICE); a.Tf = d2(C_TF); a.Tair = d2(C_TAIR); a.Qa = d2(C_QA);
+  a.swvdr = d2(C_SWVDR); a.swvdf = d2(C_SWVDF); a.swidr = d2(C_SWIDR); a.swidf = d2(C_SWIDF);
+  for (int k = 0; k < CPL_FLUXES; ++k) a.flux[k] = in2[C_FLUX + k] ? d2(C_FLUX + k) : nullptr;
+  double** const o[16] = {&a.alvdr, &a.alidr, &a.alvdf, &a.alidf, &a.albice, &a.albsno, &a.albpnd, &a.alvdf_gbm, &a.alidf_gbm,
+                          &a.alvdr_gbm, &a.alidr_gbm, &a.fresh_gbm, &a.fsalt_gbm, &a.fhocn_gbm, &a.fswthru_gbm, &a.scale_factor};
+  for (int k = 0; k < 16; ++k) *o[k] = d2(C_ALB + k);
+  a.albcnt = f->albcnt ? dcnt : nullptr;
+  coupling_prep_launch(a, s);
+  cpl_clock_.mark(2, s);
+  // ice_HaloUpdate (scale_factor, halo_info, field_loc_center, field_type_scalar) (:758-759)
+  if (halo) halo->update_r8(d2(C_SF), 1, n2, true, LOC_CENTER, KIND_SCALAR);
+
+  fan_->fork(s);
+  for (int k = 0; k < C_2D; ++k)
+    if (out2[k]) CICE_HIP(hipMemcpyAsync(out2[k], d2(k), n2 * 8, hipMemcpyDeviceToHost, cs()));
+  if (f->albcnt) CICE_HIP(hipMemcpyAsync(f->albcnt, dcnt, (size_t)f->nstreams * n2 * 8, hipMemcpyDeviceToHost, cs()));
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  cpl_clock_.read(0, 2);
 }
 
 void ColumnBatch::handover_time(bool enable, float* ms) {

@@ -22,6 +22,7 @@
 #include "ridge.h"
 #include "shortwave.h"
 #include "dedd.h"
+#include "coupling.h"
 #include "transport.h"
 #include "batch.h"
 
@@ -137,6 +138,9 @@ struct cice_ctx {
   bool have_dedd = false;
   DevBuf<double> dedd_d;
   DevBuf<int32_t> dedd_i;
+  // coupling_prep (coupling.h): what cice_coupling_init was given
+  CouplingParams cp{};
+  bool have_cpl = false;
   // device is required lazily: domain queries work on a CPU-only host
   // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
   // process may have changed the current device since the last call (another context on another GPU,

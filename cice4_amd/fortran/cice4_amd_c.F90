@@ -727,6 +727,50 @@ module cice4_amd_c
       end function
    end interface
 
+   ! coupling_prep (drivers/cice4/CICE_RunMod.F90:588-767): the mixed layer, the albedo merge, scale_fluxes
+   ! (cice4_amd/csrc/coupling.hip)
+   type, bind(C) :: cice_coupling_config
+      integer(c_int) :: scale_fluxes, oceanmixed_ice, atmbndy
+      real(c_double) :: albocn
+   end type
+
+   type, bind(C) :: cice_coupling_fields
+      integer(c_int) :: ncat, state_resident, alb_resident, bound, nstreams
+      type(c_ptr) :: tmask
+      type(c_ptr) :: alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, albpndn, aicen
+      type(c_ptr) :: coszen, aice, Tf, Tair, Qa, swvdr, swvdf, swidr, swidf
+      type(c_ptr) :: strairxT, strairyT, fsens, flat, fswabs, flwout, evap, Tref, Qref, fresh, fsalt, fhocn
+      type(c_ptr) :: fswthru
+      type(c_ptr) :: alvdr, alidr, alvdf, alidf, albice, albsno, albpnd
+      type(c_ptr) :: alvdf_gbm, alidf_gbm, alvdr_gbm, alidr_gbm, fresh_gbm, fsalt_gbm, fhocn_gbm, fswthru_gbm, scale_factor
+      type(c_ptr) :: albcnt
+      type(c_ptr) :: potT, uatm, vatm, wind, zlvl, rhoa, flw, hmix
+      type(c_ptr) :: sst, qdp
+      type(c_ptr) :: frzmlt, flwout_ocn, fsens_ocn, flat_ocn, evap_ocn, strairx_ocn, strairy_ocn, Tref_ocn, Qref_ocn
+      type(c_ptr) :: alvdr_ocn, alidr_ocn, alvdf_ocn, alidf_ocn
+      type(c_ptr) :: delt, delq, shcoef, lhcoef
+   end type
+
+   interface
+      integer(c_int) function cice_coupling_init(ctx, cfg) bind(C, name='cice_coupling_init')
+         import
+         type(c_ptr), value :: ctx
+         type(cice_coupling_config), intent(in) :: cfg
+      end function
+      integer(c_int) function cice_coupling_prep(ctx, dt, f) bind(C, name='cice_coupling_prep')
+         import
+         type(c_ptr), value :: ctx
+         real(c_double), value :: dt
+         type(cice_coupling_fields), intent(in) :: f
+      end function
+      integer(c_int) function cice_coupling_times(ctx, enable, ms) bind(C, name='cice_coupling_times')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: enable
+         real(c_float), intent(out) :: ms(2)
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

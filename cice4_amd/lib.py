@@ -163,6 +163,31 @@ class PrepRadiationFields(C.Structure):
     _fields_ = [("ncat", C.c_int), ("sw_resident", C.c_int)] + [(n, C.c_void_p) for n in PREP_RADIATION_PTRS]
 
 
+class CouplingConfig(C.Structure):
+    _fields_ = [("scale_fluxes", C.c_int), ("oceanmixed_ice", C.c_int), ("atmbndy", C.c_int), ("albocn", C.c_double)]
+
+
+# cice_coupling_fields in the order of the struct: tmask (int32), then doubles
+COUPLING_CAT_IN = ("alvdrn", "alidrn", "alvdfn", "alidfn", "albicen", "albsnon", "albpndn", "aicen")
+COUPLING_IN = ("coszen", "aice", "Tf", "Tair", "Qa", "swvdr", "swvdf", "swidr", "swidf")
+COUPLING_FLUXES = ("strairxT", "strairyT", "fsens", "flat", "fswabs", "flwout", "evap", "Tref", "Qref", "fresh", "fsalt",
+                   "fhocn", "fswthru")
+COUPLING_OUT = ("alvdr", "alidr", "alvdf", "alidf", "albice", "albsno", "albpnd", "alvdf_gbm", "alidf_gbm", "alvdr_gbm",
+                "alidr_gbm", "fresh_gbm", "fsalt_gbm", "fhocn_gbm", "fswthru_gbm", "scale_factor")
+COUPLING_MIX_IN = ("potT", "uatm", "vatm", "wind", "zlvl", "rhoa", "flw", "hmix")
+COUPLING_MIX_IO = ("sst", "qdp")
+COUPLING_MIX_OUT = ("frzmlt", "flwout_ocn", "fsens_ocn", "flat_ocn", "evap_ocn", "strairx_ocn", "strairy_ocn", "Tref_ocn",
+                    "Qref_ocn", "alvdr_ocn", "alidr_ocn", "alvdf_ocn", "alidf_ocn")
+COUPLING_MIX_OPT = ("delt", "delq", "shcoef", "lhcoef")
+COUPLING_PTRS = (COUPLING_CAT_IN + COUPLING_IN + COUPLING_FLUXES + COUPLING_OUT + ("albcnt",) + COUPLING_MIX_IN +
+                 COUPLING_MIX_IO + COUPLING_MIX_OUT + COUPLING_MIX_OPT)
+
+
+class CouplingFields(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("ncat", "state_resident", "alb_resident", "bound", "nstreams")] + [
+        ("tmask", C.c_void_p)] + [(n, C.c_void_p) for n in COUPLING_PTRS]
+
+
 class ThermoFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in THERMO_STATE + THERMO_FORCING + THERMO_CAT_IN + THERMO_SW
                 + THERMO_OUT + THERMO_ONSET]
@@ -1081,6 +1106,33 @@ class Context:
         ms = (C.c_float * 1)()
         self._ck(self.lib.cice_dedd_times(self.h, int(enable), ms))
         return ms[0]
+
+    # ---- coupling_prep: the mixed layer, the albedo merge, scale_fluxes --------------------------
+    def coupling_init(self, scale_fluxes=True, oceanmixed_ice=True, atmbndy="default", albocn=0.06):
+        """cice_coupling_init (after thermo_init).  scale_fluxes=False: what a reference compiled -DAusCOM does.
+        atmbndy='constant' raises CiceError with code CICE_EUNSUPPORTED."""
+        cfg = CouplingConfig(int(scale_fluxes), int(oceanmixed_ice), {"default": 0, "constant": 1}[atmbndy], albocn)
+        self._ck(self.lib.cice_coupling_init(self.h, C.byref(cfg)))
+
+    def coupling_prep(self, dt, a, state_resident=False, alb_resident=False, bound=False, nstreams=0, ncat=NCAT):
+        """cice_coupling_prep on the batch (thermo_batch_alloc).  a: tmask (int32, (nb,ny,nx)) and the arrays of
+        COUPLING_PTRS -- per-category ones (nb,ncat,ny,nx), 2-d fields (nb,ny,nx), albcnt (nstreams,nb,ny,nx); a missing
+        key is a NULL pointer.  The fields of COUPLING_FLUXES, albcnt, sst and qdp are updated in place, those of
+        COUPLING_OUT, COUPLING_MIX_OUT and COUPLING_MIX_OPT written."""
+        f = CouplingFields()
+        f.ncat, f.state_resident, f.alb_resident, f.bound, f.nstreams = ncat, int(state_resident), int(alb_resident), \
+            int(bound), int(nstreams)
+        f.tmask = _i4(a["tmask"]) if a.get("tmask") is not None else None
+        for n in COUPLING_PTRS:
+            setattr(f, n, _f8(a[n]) if a.get(n) is not None else None)
+        self._ck(self.lib.cice_coupling_prep(self.h, C.c_double(dt), C.byref(f)))
+
+    def coupling_times(self, enable=True):
+        """cice_coupling_times: switch the event timing on / off; (k_ocean_mixed_layer, k_coupling_prep) ms of the last
+        timed call"""
+        ms = (C.c_float * 2)()
+        self._ck(self.lib.cice_coupling_times(self.h, int(enable), ms))
+        return tuple(ms)
 
     def therm2_itd_times(self, enable=True):
         """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""

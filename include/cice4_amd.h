@@ -813,6 +813,69 @@ int cice_step_radiation_dedd(cice_ctx *ctx, const cice_radiation_dedd_fields *f)
 /* Measurement aid (scripts/dedd_cost.py), off by default: ms[0] the device time (ms) of the last timed k_shortwave_dedd. */
 int cice_dedd_times(cice_ctx *ctx, int enable, float ms[1]);
 
+/* ---- coupling_prep (drivers/cice4/CICE_RunMod.F90:588-767): the mixed layer (ocean_mixed_layer, source/ice_ocean.F90:
+ * 64-234), the area-weighted merge of the per-category albedos, the *_gbm copies, scale_factor and scale_fluxes
+ * (source/ice_flux.F90:776-888) on the device, on the batch of cice_thermo_batch_alloc ----
+ * cice_coupling_init comes after cice_thermo_init (CICE_EINVAL otherwise).  scale_fluxes: 1 the stand-alone build; 0 what
+ * a reference compiled -DAusCOM does (drivers/access-om/CICE_RunMod.F90:927-959 skips the call).  oceanmixed_ice: the
+ * namelist's; 0 skips the mixed layer.  atmbndy: 0 'default'; 1 'constant' is CICE_EUNSUPPORTED: in that branch the
+ * reference never sets its local arrays delt and delq (ice_ocean.F90:139-150) and then multiplies by them (:207-208).
+ * albocn: the ocean albedo of ice_constants (0.06).  sfcflux_to_ocn (:747) is empty unless the reference is compiled
+ * -DCICE_IN_NEMO: there is nothing to call. */
+typedef struct {
+  int scale_fluxes, oceanmixed_ice, atmbndy;
+  double albocn;
+} cice_coupling_config;
+int cice_coupling_init(cice_ctx *ctx, const cice_coupling_config *cfg);
+/* coupling_prep as ONE call, every cell of every block, ghost cells included (the reference loops 1..nx_block,
+ * 1..ny_block here).  Per-category arrays (nx,ny,ncat,nb); 2-d fields (nx,ny,nb); albcnt (nx,ny,nb,nstreams).
+ * Order: the mixed layer first (it reads fhocn, fswthru and aice before they are scaled), then the merge and scaling.
+ *   albcnt (may be NULL; CICE_EINVAL if given with nstreams = 0) gets 1 added where coszen > puny, for n = 1..nstreams.
+ *   alvdr, alidr, alvdf, alidf: the running sums of al*n * aicen over n = 1..ncat; albice, albsno, albpnd: the same where
+ *   coszen > puny, else 0.  albpndn may be NULL and then counts as zeros.  The eight *_gbm are the unscaled copies;
+ *   scale_factor = swvdr (1 - alvdr_gbm) + swvdf (1 - alvdf_gbm) + swidr (1 - alidr_gbm) + swidf (1 - alidf_gbm).
+ *   scale_fluxes = 1: where tmask and aice > 0 the 13 fields strairxT ... fswthru and the four albedos are multiplied by
+ *   1 / aice; elsewhere they are 0, flwout = -stefan_boltzmann (Tf + Tffresh)**4, Tref = Tair, Qref = Qa.
+ *   scale_fluxes = 0: fresh, fsalt, fhocn, fswthru are read (for their *_gbm copies) and not written; strairxT ... Qref,
+ *   tmask, aice, Tf, Tair, Qa are not touched and may be NULL; the four albedos are the unscaled sums.
+ * The mixed layer (oceanmixed_ice = 1; otherwise its fields may be NULL): land cells (tmask = 0) get sst = frzmlt =
+ *   flwout_ocn = fsens_ocn = flat_ocn = evap_ocn = 0 and, as atmo_boundary_layer zeroes its whole block first, zeros in
+ *   strairx_ocn, strairy_ocn, Tref_ocn, Qref_ocn (and delt, delq, shcoef, lhcoef); their qdp passes through.  Ocean cells:
+ *   atmo_boundary_layer('ocn') with Tsf = sst, then ice_ocean.F90:190-231.  The four al*_ocn are albocn on every cell.
+ *   delt, delq, shcoef, lhcoef -- the reference's local arrays -- are optional outputs (each may be NULL).
+ * state_resident = 1: aicen is what cice_step_ridge or cice_step_therm2_cleanup left on the device (the record
+ *   cice_step_radiation's state_resident = 1 checks: CICE_EINVAL without it); the host aicen is not read, the record stays.
+ * alb_resident = 1: the per-category albedos are what the last successful cice_step_radiation or cice_step_radiation_dedd
+ *   left in its buffer on the device; the seven host pointers are not read; after cice_step_radiation albpndn counts as
+ *   zeros.  CICE_EINVAL if the batch holds no such record: none was made, or a radiation call of either scheme that failed
+ *   behind its argument checks or zero-filled under calc_Tsfc = 0, a cice_prep_radiation (which stages its aicen in the
+ *   ccsm3 scheme's buffer) or a new cice_thermo_batch_alloc has ended it.
+ * With both 0 everything is uploaded, into buffers of this entry's own: the batch's state and both records are left as
+ *   they are.
+ * bound = 1: the reference's closing ice_HaloUpdate(scale_factor, center, scalar) runs on the device copy through the
+ *   context's domain before the download (CICE_EINVAL without one of the batch's layout); 0 skips it.
+ * One download of all outputs at the end.  Arguments that are intent(in) in the reference are never written. */
+typedef struct {
+  int ncat, state_resident, alb_resident, bound, nstreams;
+  const int32_t *tmask;
+  const double *alvdrn, *alidrn, *alvdfn, *alidfn, *albicen, *albsnon, *albpndn, *aicen;
+  const double *coszen, *aice, *Tf, *Tair, *Qa, *swvdr, *swvdf, *swidr, *swidf;
+  double *strairxT, *strairyT, *fsens, *flat, *fswabs, *flwout, *evap, *Tref, *Qref, *fresh, *fsalt, *fhocn,
+      *fswthru;                                                       /* in / out */
+  double *alvdr, *alidr, *alvdf, *alidf, *albice, *albsno, *albpnd;   /* out */
+  double *alvdf_gbm, *alidf_gbm, *alvdr_gbm, *alidr_gbm, *fresh_gbm, *fsalt_gbm, *fhocn_gbm, *fswthru_gbm, *scale_factor;
+  double *albcnt;                                                     /* in / out, may be NULL */
+  const double *potT, *uatm, *vatm, *wind, *zlvl, *rhoa, *flw, *hmix; /* the mixed layer */
+  double *sst, *qdp;                                                  /* in / out */
+  double *frzmlt, *flwout_ocn, *fsens_ocn, *flat_ocn, *evap_ocn, *strairx_ocn, *strairy_ocn, *Tref_ocn, *Qref_ocn;
+  double *alvdr_ocn, *alidr_ocn, *alvdf_ocn, *alidf_ocn;
+  double *delt, *delq, *shcoef, *lhcoef;                              /* optional */
+} cice_coupling_fields;
+int cice_coupling_prep(cice_ctx *ctx, double dt, const cice_coupling_fields *f);
+/* Measurement aid (scripts/coupling_cost.py), off by default: ms[0], ms[1] the device times (ms) of the last timed
+ * k_ocean_mixed_layer and k_coupling_prep. */
+int cice_coupling_times(cice_ctx *ctx, int enable, float ms[2]);
+
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
  * dependencies from ntrcr / trcr_depend (ice_init.F90:848-852: 0 area tracer, 1 ice-volume, 2 snow-volume tracer),
