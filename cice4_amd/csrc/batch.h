@@ -14,6 +14,7 @@
 #include "halo.h"
 #include "handover.h"
 #include "itd.h"
+#include "pond.h"
 #include "ridge.h"
 #include "shortwave.h"
 #include "therm.h"
@@ -146,6 +147,10 @@ class ColumnBatch {
   // or nullptr
   void coupling_prep(const CouplingParams* cp, double dt, const cice_coupling_fields* f, Halo* halo);
   void coupling_times(bool enable, float ms[2]) { cpl_clock_.query(enable, ms); }   // k_ocean_mixed_layer, k_coupling_prep
+  // compute_ponds and increment_age behind step_therm1 (pond.h); nt_volpn: the slot given to cice_pond_init, 0 none
+  void step_ponds(const ThermoParams* tp, int nt_volpn, double dt, const cice_pond_fields* f);
+  void pond_times(bool enable, float ms[1]) { pond_clock_.query(enable, ms); }      // the last timed k_pond_age
+  void pond_chain(int mode);                        // cice_pond_chain
   void radiation_chain(int mode);                   // cice_radiation_chain
   void radiation_times(bool enable, float ms[2]) {  // the last timed k_shortwave_ccsm3, k_prep_radiation
     sw_clock_.query(enable, ms);
@@ -252,6 +257,7 @@ class ColumnBatch {
     struct { const double* h; bool may_be_null; } in2[5];
     bool pond;
     const double* pondn[2];
+    const double* pond_dev[2];               // cice_pond_chain: the device copies of pondn, or NULL: pondn is uploaded
     int nout;
     double* out[7];
     SwArrays sw;
@@ -273,6 +279,16 @@ class ColumnBatch {
   DevBuf<double> cpl_b_;                     // the 2-d fields, albcnt, and the uploaded per-category arrays
   DevBuf<int32_t> cpl_bi_;                   // tmask
   StageClock<2> cpl_clock_;
+  // pond stage.  therm1_state_: aicen_, vicen_, vsnon_, the surface temperature plane of trcrn_ and the meltt / melts
+  // planes of out15_ hold what the last successful step_therm1 left -- whatever rewrites one of them ends the record.
+  // pond_armed_: pond_b_ holds the apondn, hpondn the last step_ponds downloaded to the host arrays pond_host_
+  // (cice_pond_chain mode 1).
+  bool therm1_state_ = false;
+  DevBuf<double> pond_b_;                    // volpn, iage, apondn, hpondn, six planes of uploaded state; frain
+  StageClock<1> pond_clock_;
+  int pond_mode_ = 0;
+  bool pond_armed_ = false;
+  const double* pond_host_[2] = {};
   hipEvent_t ho_ev_[2] = {};                 // around k_state_from_transport (handover_time)
   bool ho_timed_ = false, ho_pending_ = false;
   float ho_ms_ = 0.0f;

@@ -77,6 +77,8 @@ void ColumnBatch::alloc(hipStream_t stream, CopyFan& fan, int nx, int ny, int nb
   nx_ = nx; ny_ = ny; nb_ = nb;
   kept_aicen_init_ = false;
   therm2_state_ = false;
+  therm1_state_ = false;
+  pond_armed_ = false;
   forget_sw();
   alb_scheme_ = ALB_NONE;
   const size_t np = (size_t)nx * ny, n2 = np * nb, nc = n2 * NCAT;
@@ -163,6 +165,7 @@ void ColumnBatch::upload_fields(const ThermoParams* tp, const cice_thermo_fields
 void ColumnBatch::upload(const ThermoParams* tp, const cice_thermo_fields* h) {
   kept_aicen_init_ = false;
   therm2_state_ = false;
+  therm1_state_ = false;
   forget_sw();
   upload_fields(tp, h, true, true);
   CICE_HIP(hipStreamSynchronize(stream_));
@@ -222,6 +225,7 @@ void ColumnBatch::step(const ThermoParams* tp, double dt, double yday, long long
                        int32_t* jstop, int32_t* nstop, int32_t* bstop, float* elapsed_ms) {
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
   therm2_state_ = false;
+  therm1_state_ = false;
   forget_sw();                         // the column update writes the shortwave buffers
   unsigned long long h[THERMO_STATUS_WORDS];
   StageClock<1> clock;                 // of this call: no events without elapsed_ms
@@ -305,6 +309,7 @@ void ColumnBatch::step_therm1(const ThermoParams* tp, double chio, double dt, do
   CICE_REQUIRE(fz->aice && fz->frzmlt && fz->sst && fz->Tf && fz->strocnxT && fz->strocnyT, "NULL frzmlt input");
   hipStream_t s = stream_;
   therm2_state_ = false;
+  therm1_state_ = false;
   // cice_radiation_chain: the five shortwave arrays are on the device already if they are the host arrays the radiation
   // stage downloaded to; consumed or not, the record ends here (the column update writes those buffers)
   const bool sw_kept = sw_armed_ && st->fswsfc == sw_host_[0] && st->fswint == sw_host_[1] && st->fswthrun == sw_host_[2] &&
@@ -376,6 +381,7 @@ void ColumnBatch::step_therm1(const ThermoParams* tp, double chio, double dt, do
   CICE_HIP(hipStreamSynchronize(s));
   if (n_updates) *n_updates = status_count(h);
   decode_err(h[0], nx_, NCAT, nullptr, nullptr, l_stop, istop, jstop, nstop, bstop);
+  therm1_state_ = !*l_stop;            // the updated state and the per-category melt are on the device (step_ponds)
 }
 
 // the record words once the stream has run dry
@@ -401,6 +407,7 @@ void ColumnBatch::step_therm2_itd(const ThermoParams* tp, const ItdParams* ip, d
                "cice_step_therm2_itd: aicen_init = NULL needs a cice_step_therm1 call on this batch in front");
   hipStream_t s = stream_;
   therm2_state_ = false;
+  therm1_state_ = false;
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
   if (itd_b_.n < 2 * nc + 12 * n2) itd_b_.alloc(2 * nc + 12 * n2);
   if (itd_bi_.n < n2 + (size_t)nb_) itd_bi_.alloc(n2 + (size_t)nb_);
@@ -528,6 +535,7 @@ void ColumnBatch::column_stages(const ItdParams* ip, double dt, const cice_therm
                "cice_step_therm2_cleanup: state_resident needs a cice_step_therm2_itd call on this batch in front");
   hipStream_t s = stream_;
   therm2_state_ = false;
+  therm1_state_ = false;
   const size_t np = (size_t)nx_ * ny_, n2 = np * nb_;
   const int ntr = ip->ntrcr;
   enum { C_AICE = 0, C_AICE0, C_VICE, C_VSNO, C_EICE, C_ESNO, C_FRESH, C_FSALT, C_FHOCN, C_DAIDTT, C_DVIDTT, C_TRCR,
@@ -774,12 +782,16 @@ void ColumnBatch::radiation_stage(const ThermoParams& tp, const RadScheme& r, La
   fan_->fork(s);
   if (!resident) {                     // of the state the scheme reads these four; the rest of the batch's state is stale now
     therm2_state_ = false;
+    therm1_state_ = false;
     move_state(r.state, ST_AICEN | ST_VICEN | ST_VSNON, tp.nt_Tsfc - 1, tp.nt_Tsfc, hipMemcpyHostToDevice);
   }
   for (int k = 0; k < 5; ++k)
     if (r.in2[k].h) CICE_HIP(hipMemcpyAsync(p2 + k * n2, r.in2[k].h, n2 * 8, hipMemcpyHostToDevice, cs()));
   for (int k = 0; k < 2 && r.pond; ++k)
-    CICE_HIP(hipMemcpyAsync(pc + (r.nout + k) * nc, r.pondn[k], nc * 8, hipMemcpyHostToDevice, cs()));
+    if (r.pond_dev[k])                 // cice_pond_chain: the pond stage's device copy is the host array's
+      CICE_HIP(hipMemcpyAsync(pc + (r.nout + k) * nc, r.pond_dev[k], nc * 8, hipMemcpyDeviceToDevice, cs()));
+    else
+      CICE_HIP(hipMemcpyAsync(pc + (r.nout + k) * nc, r.pondn[k], nc * 8, hipMemcpyHostToDevice, cs()));
   fan_->join();
   r.clock->mark(0, s);
   launch(p2, pc);
@@ -817,7 +829,7 @@ void ColumnBatch::step_radiation(const ThermoParams* tp, const ShortwaveParams* 
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
   CICE_REQUIRE(sp, "cice_shortwave_init has not been called");
   const RadScheme r{"cice_step_radiation", f->state_resident, {f->aicen, f->vicen, f->vsnon, nullptr, nullptr, f->trcrn},
-                    &rad_b_, R_2D, 6, {{f->swvdr}, {f->swvdf}, {f->swidr}, {f->swidf}, {f->ocn_albedo, true}}, false, {}, 6,
+                    &rad_b_, R_2D, 6, {{f->swvdr}, {f->swvdf}, {f->swidr}, {f->swidf}, {f->ocn_albedo, true}}, false, {}, {}, 6,
                     {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon},
                     {{f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn}}, &sw_clock_, true, f->coszen};
   radiation_stage(*tp, r, [&](double* p2, double* pc) {
@@ -886,6 +898,10 @@ void ColumnBatch::prep_radiation(const ThermoParams* tp, const cice_prep_radiati
   keep_sw(sw);
 }
 
+// planes of pond_b_ ((nx, ny, ncat, nb) each; behind them frain, (nx, ny, nb)): the two tracers, the pond fraction and depth,
+// and what state_resident = 0 uploads
+enum { P_VOLPN = 0, P_IAGE, P_APOND, P_HPOND, P_AICEN, P_VICEN, P_VSNON, P_TSFC, P_MELTT, P_MELTS, P_PLANES };
+
 // planes of dedd_b_: coszen and the four sw fields (nx, ny, nb each), then nine (nx, ny, ncat, nb) arrays -- the four
 // albedos, albicen, albsnon, albpndn, and the inputs apondn, hpondn
 enum { D_COSZEN = 0, D_SWVDR, D_SWVDF, D_SWIDR, D_SWIDF, D_2D };
@@ -895,9 +911,13 @@ enum { D_COSZEN = 0, D_SWVDR, D_SWVDF, D_SWIDR, D_SWIDF, D_2D };
 void ColumnBatch::step_radiation_dedd(const ThermoParams* tp, const DeddParams* dp, const cice_radiation_dedd_fields* f) {
   CICE_REQUIRE(tp, "cice_thermo_init has not been called");
   CICE_REQUIRE(dp, "cice_shortwave_dedd_init has not been called");
+  // cice_pond_chain: apondn and hpondn are on the device already if they are the host arrays the pond stage downloaded to
+  const bool chained = pond_armed_ && dp->tr_pond && f->apondn == pond_host_[0] && f->hpondn == pond_host_[1];
+  const size_t ncp = (size_t)nx_ * ny_ * nb_ * NCAT;
   const RadScheme r{"cice_step_radiation_dedd", f->state_resident, {f->aicen, f->vicen, f->vsnon, nullptr, nullptr, f->trcrn},
                     &dedd_b_, D_2D, 9, {{f->coszen}, {f->swvdr}, {f->swvdf}, {f->swidr}, {f->swidf}}, dp->tr_pond != 0,
-                    {f->apondn, f->hpondn}, 7, {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon, f->albpndn},
+                    {f->apondn, f->hpondn},
+                    {chained ? pond_b_.p + P_APOND * ncp : nullptr, chained ? pond_b_.p + P_HPOND * ncp : nullptr}, 7, {f->alvdrn, f->alidrn, f->alvdfn, f->alidfn, f->albicen, f->albsnon, f->albpndn},
                     {{f->fswsfcn, f->fswintn, f->fswthrun, f->Sswabsn, f->Iswabsn}}, &dedd_clock_, false, nullptr};
   radiation_stage(*tp, r, [&](double* p2, double* pc) {
     const size_t nc = (size_t)nx_ * ny_ * nb_ * NCAT;
@@ -1055,6 +1075,80 @@ void ColumnBatch::coupling_prep(const CouplingParams* cp, double dt, const cice_
   fan_->join();
   CICE_HIP(hipStreamSynchronize(s));
   cpl_clock_.read(0, 2);
+}
+
+// compute_ponds and increment_age behind step_therm1 (CICE_RunMod.F90:449-454, :550-559): see include/cice4_amd.h.  The
+// capi has checked the flags against the tracers and the arrays they require.
+void ColumnBatch::step_ponds(const ThermoParams* tp, int nt_volpn, double dt, const cice_pond_fields* f) {
+  CICE_REQUIRE(tp, "cice_step_ponds: cice_thermo_init has not been called");
+  const bool resident = f->state_resident == 1, ponds = f->ponds != 0, age = f->age != 0;
+  CICE_REQUIRE(!resident || therm1_state_,
+               "cice_step_ponds: state_resident needs a cice_step_therm1 call without a stop on this batch in front");
+  hipStream_t s = stream_;
+  pond_armed_ = false;
+  const size_t np = (size_t)nx_ * ny_, n2 = np * nb_, nc = n2 * NCAT;
+  if (pond_b_.n != P_PLANES * nc + n2) pond_b_.alloc(P_PLANES * nc + n2);
+  auto pl = [&](int k) { return pond_b_.p + (size_t)k * nc; };
+  double* const dfrain = pl(P_PLANES);
+  // plane `it` of the caller's trcrn(nx, ny, max_ntrcr, ncat, nb) and plane `k` of pond_b_, one strided copy
+  auto tracer_plane = [&](int it, int k, hipMemcpyKind kind) {
+    double* h = f->trcrn + (size_t)it * np;
+    const size_t hp = (size_t)NTRCR * np * 8, dp = np * 8;
+    if (kind == hipMemcpyHostToDevice) CICE_HIP(hipMemcpy2DAsync(pl(k), dp, h, hp, np * 8, (size_t)NCAT * nb_, kind, cs()));
+    else CICE_HIP(hipMemcpy2DAsync(h, hp, pl(k), dp, np * 8, (size_t)NCAT * nb_, kind, cs()));
+  };
+  auto up = [&](int k, const double* h) { CICE_HIP(hipMemcpyAsync(pl(k), h, nc * 8, hipMemcpyHostToDevice, cs())); };
+  fan_->fork(s);
+  if (ponds) {
+    CICE_HIP(hipMemcpyAsync(dfrain, f->frain, n2 * 8, hipMemcpyHostToDevice, cs()));
+    tracer_plane(nt_volpn - 1, P_VOLPN, hipMemcpyHostToDevice);
+    up(P_APOND, f->apondn); up(P_HPOND, f->hpondn);
+  }
+  if (age) tracer_plane(tp->nt_iage - 1, P_IAGE, hipMemcpyHostToDevice);
+  if (!resident) {
+    up(P_AICEN, f->aicen);
+    if (ponds) {
+      up(P_VICEN, f->vicen); up(P_VSNON, f->vsnon); up(P_MELTT, f->melttn); up(P_MELTS, f->meltsn);
+      tracer_plane(tp->nt_Tsfc - 1, P_TSFC, hipMemcpyHostToDevice);
+    }
+  }
+  fan_->join();
+  PondArgs a{};
+  a.nx = nx_; a.np = (int)np; a.ncat = NCAT; a.nb = nb_; a.ponds = ponds; a.age = age; a.dt = dt;
+  a.blk = blk_.p;
+  a.volpn_planes = 1; a.iage_planes = 1;
+  a.volpn = pl(P_VOLPN); a.iage = pl(P_IAGE); a.apondn = pl(P_APOND); a.hpondn = pl(P_HPOND); a.frain = dfrain;
+  if (resident) {                      // out15_: fsurfn ... fhocnn, meltt, melts, ... (ThermoArgs' order)
+    a.aicen = aicen_.p; a.vicen = vicen_.p; a.vsnon = vsnon_.p;
+    a.Tsfc = trcrn_.p + (size_t)(tp->nt_Tsfc - 1) * np; a.tsfc_planes = NTRCR;
+    a.meltt = out15_.p + 10 * nc; a.melts = out15_.p + 11 * nc;
+  } else {
+    a.aicen = pl(P_AICEN); a.vicen = pl(P_VICEN); a.vsnon = pl(P_VSNON); a.Tsfc = pl(P_TSFC); a.tsfc_planes = 1;
+    a.meltt = pl(P_MELTT); a.melts = pl(P_MELTS);
+  }
+  pond_clock_.mark(0, s);
+  pond_launch(a, s);
+  pond_clock_.mark(1, s);
+  fan_->fork(s);
+  if (ponds) {
+    CICE_HIP(hipMemcpyAsync(f->apondn, pl(P_APOND), nc * 8, hipMemcpyDeviceToHost, cs()));
+    CICE_HIP(hipMemcpyAsync(f->hpondn, pl(P_HPOND), nc * 8, hipMemcpyDeviceToHost, cs()));
+    tracer_plane(nt_volpn - 1, P_VOLPN, hipMemcpyDeviceToHost);
+  }
+  if (age) tracer_plane(tp->nt_iage - 1, P_IAGE, hipMemcpyDeviceToHost);
+  fan_->join();
+  CICE_HIP(hipStreamSynchronize(s));
+  pond_clock_.read(0, 1);
+  if (ponds) {
+    pond_host_[0] = f->apondn; pond_host_[1] = f->hpondn;
+    pond_armed_ = pond_mode_ == 1;
+  }
+}
+
+void ColumnBatch::pond_chain(int mode) {
+  CICE_REQUIRE(mode == 0 || mode == 1, "cice_pond_chain: mode must be 0 or 1");
+  pond_mode_ = mode;
+  pond_armed_ = false;
 }
 
 void ColumnBatch::handover_time(bool enable, float* ms) {

@@ -23,6 +23,7 @@
 #include "shortwave.h"
 #include "dedd.h"
 #include "coupling.h"
+#include "pond.h"
 #include "transport.h"
 #include "batch.h"
 
@@ -141,6 +142,11 @@ struct cice_ctx {
   // coupling_prep (coupling.h): what cice_coupling_init was given
   CouplingParams cp{};
   bool have_cpl = false;
+  // melt ponds and ice age (pond.h): the slot given to cice_pond_init (0: no pond tracer); staging of the block-wise entries
+  int nt_volpn = 0;
+  bool have_pond = false;
+  DevBuf<double> pond_d;
+  DevBuf<int32_t> pond_i;
   // device is required lazily: domain queries work on a CPU-only host
   // Every C-ABI entry binds the calling thread to this context's device first (CICE_TRY): the host
   // process may have changed the current device since the last call (another context on another GPU,

@@ -771,6 +771,59 @@ module cice4_amd_c
       end function
    end interface
 
+   ! melt ponds and ice age (source/ice_meltpond.F90: compute_ponds; source/ice_age.F90: increment_age) behind
+   ! cice_step_therm1 (cice4_amd/csrc/pond.hip)
+   type, bind(C) :: cice_pond_fields
+      integer(c_int) :: ncat, state_resident, ponds, age
+      type(c_ptr) :: frain
+      type(c_ptr) :: trcrn
+      type(c_ptr) :: apondn, hpondn
+      type(c_ptr) :: aicen, vicen, vsnon, melttn, meltsn
+   end type
+
+   interface
+      integer(c_int) function cice_pond_init(ctx, nt_volpn) bind(C, name='cice_pond_init')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nt_volpn
+      end function
+      integer(c_int) function cice_compute_ponds(ctx, nx_block, ny_block, ilo, ihi, jlo, jhi, dt, meltt, melts, frain, &
+                                                 aicen, vicen, vsnon, trcrn, apondn, hpondn) bind(C, name='cice_compute_ponds')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, ilo, ihi, jlo, jhi
+         real(c_double), value :: dt
+         real(c_double), intent(in) :: meltt(*), melts(*), frain(*), aicen(*), vicen(*), vsnon(*)
+         real(c_double), intent(inout) :: trcrn(*), apondn(*), hpondn(*)
+      end function
+      integer(c_int) function cice_increment_age(ctx, nx_block, ny_block, dt, icells, indxi, indxj, iage) &
+                                                 bind(C, name='cice_increment_age')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nx_block, ny_block, icells
+         real(c_double), value :: dt
+         integer(c_int), intent(in) :: indxi(*), indxj(*)
+         real(c_double), intent(inout) :: iage(*)
+      end function
+      integer(c_int) function cice_step_ponds(ctx, dt, f) bind(C, name='cice_step_ponds')
+         import
+         type(c_ptr), value :: ctx
+         real(c_double), value :: dt
+         type(cice_pond_fields), intent(in) :: f
+      end function
+      integer(c_int) function cice_pond_times(ctx, enable, ms) bind(C, name='cice_pond_times')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: enable
+         real(c_float), intent(out) :: ms(1)
+      end function
+      integer(c_int) function cice_pond_chain(ctx, mode) bind(C, name='cice_pond_chain')
+         import
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: mode
+      end function
+   end interface
+
    ! one context per MPI task (= per GPU), shared by the drop-in modules
    type(c_ptr), save :: cice_gpu_ctx = c_null_ptr
    ! set by the boundary module (rccl/ice_boundary.F90) once it has built the device topology for the

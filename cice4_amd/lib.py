@@ -188,6 +188,14 @@ class CouplingFields(C.Structure):
         ("tmask", C.c_void_p)] + [(n, C.c_void_p) for n in COUPLING_PTRS]
 
 
+# cice_pond_fields in the order of the struct
+POND_PTRS = ("frain", "trcrn", "apondn", "hpondn", "aicen", "vicen", "vsnon", "melttn", "meltsn")
+
+
+class PondFields(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("ncat", "state_resident", "ponds", "age")] + [(n, C.c_void_p) for n in POND_PTRS]
+
+
 class ThermoFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in THERMO_STATE + THERMO_FORCING + THERMO_CAT_IN + THERMO_SW
                 + THERMO_OUT + THERMO_ONSET]
@@ -1133,6 +1141,47 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(self.lib.cice_coupling_times(self.h, int(enable), ms))
         return tuple(ms)
+
+    # ---- melt ponds and ice age: compute_ponds, increment_age behind step_therm1 -------------------
+    def pond_init(self, nt_volpn=0):
+        """cice_pond_init (after thermo_init, which supplies nt_Tsfc, tr_iage, nt_iage).  nt_volpn: the 1-based slot of the
+        pond volume tracer; 0: no pond tracer (only the age part may be asked for)."""
+        self._ck(self.lib.cice_pond_init(self.h, int(nt_volpn)))
+
+    def compute_ponds(self, ilo, ihi, jlo, jhi, dt, a):
+        """cice_compute_ponds on one block and category.  a: meltt, melts, frain, aicen, vicen, vsnon (ny,nx) in; trcrn
+        (max_ntrcr,ny,nx), apondn, hpondn (ny,nx) updated in place on the cells with aicen > puny of ilo..ihi, jlo..jhi."""
+        ny, nx = a["aicen"].shape
+        self._ck(self.lib.cice_compute_ponds(self.h, nx, ny, ilo, ihi, jlo, jhi, C.c_double(dt),
+                                             *[_f8(a[k]) for k in ("meltt", "melts", "frain", "aicen", "vicen", "vsnon",
+                                                                   "trcrn", "apondn", "hpondn")]))
+
+    def increment_age(self, dt, icells, indxi, indxj, iage):
+        """cice_increment_age on one block and category: iage (ny,nx) + dt on the cells of the list, in place."""
+        ny, nx = iage.shape
+        self._ck(self.lib.cice_increment_age(self.h, nx, ny, C.c_double(dt), icells, _i4(indxi), _i4(indxj), _f8(iage)))
+
+    def step_ponds(self, dt, a, state_resident=False, ponds=True, age=True, ncat=NCAT):
+        """cice_step_ponds on the batch (thermo_batch_alloc).  a: the arrays of POND_PTRS -- frain (nb,ny,nx), trcrn
+        (nb,ncat,max_ntrcr,ny,nx), the others (nb,ncat,ny,nx); a missing key is a NULL pointer.  apondn, hpondn and the
+        planes nt_volpn, nt_iage of trcrn are updated in place; with state_resident aicen, vicen, vsnon, melttn, meltsn
+        are not read (what the last step_therm1 left on the device is)."""
+        f = PondFields()
+        f.ncat, f.state_resident, f.ponds, f.age = ncat, int(state_resident), int(ponds), int(age)
+        for n in POND_PTRS:
+            setattr(f, n, _f8(a[n]) if a.get(n) is not None else None)
+        self._ck(self.lib.cice_step_ponds(self.h, C.c_double(dt), C.byref(f)))
+
+    def pond_times(self, enable=True):
+        """cice_pond_times: switch the event timing on / off; the device time (ms) of the last timed k_pond_age"""
+        ms = (C.c_float * 1)()
+        self._ck(self.lib.cice_pond_times(self.h, int(enable), ms))
+        return ms[0]
+
+    def pond_chain(self, mode):
+        """cice_pond_chain: 1: a step_radiation_dedd under tr_pond that is given the apondn, hpondn arrays the last
+        step_ponds downloaded to reads the device copies instead of uploading them; 0 (the default): off."""
+        self._ck(self.lib.cice_pond_chain(self.h, int(mode)))
 
     def therm2_itd_times(self, enable=True):
         """cice_therm2_itd_times: switch the event timing of the stage's kernels on / off; the times (ms) of the last timed call"""

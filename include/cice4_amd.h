@@ -876,6 +876,65 @@ int cice_coupling_prep(cice_ctx *ctx, double dt, const cice_coupling_fields *f);
  * k_ocean_mixed_layer and k_coupling_prep. */
 int cice_coupling_times(cice_ctx *ctx, int enable, float ms[2]);
 
+/* ---- melt ponds and ice age: compute_ponds (source/ice_meltpond.F90:88-229) and increment_age (source/ice_age.F90:
+ * 87-123), the two calls of step_therm1's category loop (drivers/cice4/CICE_RunMod.F90:449-454, :550-559) that
+ * cice_step_therm1 leaves out, as a stage of their own BEHIND it (thermo_vertical neither reads nor writes the age tracer,
+ * and aicen is intent(in) there: the list aicen > puny on ilo..ihi, jlo..jhi is the same before and after) ----
+ * cice_pond_init comes after cice_thermo_init (CICE_EINVAL otherwise), which supplies nt_Tsfc, tr_iage and nt_iage.
+ * nt_volpn: the 1-based slot of the pond volume among the tracers, 1..CICE_MAX_NTRCR and neither nt_Tsfc nor (under
+ * tr_iage) nt_iage; 0: no pond tracer, only the age part may be asked for.  The caller's condition `tr_pond .and.
+ * shortwave == 'dEdd'` stays the caller's.
+ * What both routines do, on the cells with aicen > puny of the block's physical domain only -- every other word of apondn,
+ * hpondn and the tracers keeps what it held, stale values included:
+ *   hi = vicen/aicen < 0.1: apondn = hpondn = 0, and the volume tracer is NOT written (it keeps its old value);
+ *   else volpn = volpn + 0.1 (meltt rhoi/rhofresh + melts rhos/rhofresh + frain dt/rhofresh), times
+ *     exp(0.01 max(-2 - Tsfc, 0) / -2), max(., 0); apondn = min(sqrt(volpn/0.8), 1); hpondn = min(0.8 apondn, 0.9 hi);
+ *     volpn = hpondn apondn goes back into the tracer; then apondn = 0 where vsnon/aicen > puny (hpondn stays);
+ *   iage = iage + dt.
+ * Tsfc, vicen, vsnon are the values AFTER thermo_vertical.  Every step is one correctly rounded operation or the restated
+ * exp: the words are meant to be the compiled reference's, signs of zero included. */
+int cice_pond_init(cice_ctx *ctx, int nt_volpn);
+/* Drop-in for `call compute_ponds(...)`: one block, one category, host pointers, the reference's argument order with dt
+ * (its module variable of ice_calendar) in front of the fields; arrays (nx_block,ny_block), trcrn (nx_block,ny_block,
+ * max_ntrcr) of which the planes nt_Tsfc (read) and nt_volpn (read, written) travel. */
+int cice_compute_ponds(cice_ctx *ctx, int nx_block, int ny_block, int ilo, int ihi, int jlo, int jhi, double dt,
+                       const double *meltt, const double *melts, const double *frain, const double *aicen,
+                       const double *vicen, const double *vsnon, double *trcrn, double *apondn, double *hpondn);
+/* Drop-in for `call increment_age(...)`: the reference's argument list; the list is the caller's (no cell twice). */
+int cice_increment_age(cice_ctx *ctx, int nx_block, int ny_block, double dt, int icells, const int32_t *indxi,
+                       const int32_t *indxj, double *iage);
+/* Both as ONE call on the batch of cice_thermo_batch_alloc, all blocks and categories.  ponds / age (0 or 1, not both 0):
+ * what runs; ponds = 1 without a pond tracer, age = 1 without tr_iage are CICE_EINVAL.  frain (nx,ny,nb), read with ponds.
+ * trcrn (nx,ny,max_ntrcr,ncat,nb): only the planes nt_volpn (ponds) and nt_iage (age) travel, up and down; apondn, hpondn
+ * (nx,ny,ncat,nb) travel up and down with ponds.  A NULL array among those the flags require is CICE_EINVAL.
+ * state_resident = 0: aicen, vicen, vsnon, melttn, meltsn (nx,ny,ncat,nb) and the nt_Tsfc plane of trcrn are uploaded (with
+ *   age alone: aicen only), into buffers of this entry's own: the batch's state and records are untouched.
+ * state_resident = 1: aicen, vicen, vsnon, the surface temperature and the per-category meltt / melts are what the last
+ *   successful cice_step_therm1 / cice_step_therm1_abl (l_stop = 0) left in the batch; those host pointers are not read.
+ *   CICE_EINVAL without that record: none was made, or cice_thermo_batch_upload, cice_thermo_batch_step, another
+ *   cice_step_therm1*, cice_step_therm2_itd, cice_step_therm2_cleanup, cice_step_ridge, a radiation call that uploads its
+ *   state, or a new cice_thermo_batch_alloc has ended it.  The stage writes no buffer of the batch's state and ends no
+ *   record: a cice_step_therm2_itd(state_resident = 1) behind it finds what it would have found without it.
+ * One download at the end: apondn, hpondn, the nt_volpn plane (ponds); the nt_iage plane (age). */
+typedef struct {
+  int ncat, state_resident, ponds, age;
+  const double *frain;
+  double *trcrn;                                        /* in / out: the planes nt_volpn, nt_iage */
+  double *apondn, *hpondn;                              /* in / out */
+  const double *aicen, *vicen, *vsnon, *melttn, *meltsn; /* state_resident = 0 only */
+} cice_pond_fields;
+int cice_step_ponds(cice_ctx *ctx, double dt, const cice_pond_fields *f);
+/* Measurement aid (scripts/pond_cost.py), off by default: ms[0] the device time (ms) of the last timed k_pond_age. */
+int cice_pond_times(cice_ctx *ctx, int enable, float ms[1]);
+/* ponds -> radiation WITHOUT the upload of apondn and hpondn.  mode 0 (the default) is off, 1 is on, other values are
+ * CICE_EINVAL.  On: a cice_step_ponds with ponds = 1 that returns CICE_OK records the two host arrays it downloaded to; a
+ * cice_step_radiation_dedd under tr_pond = 1 whose apondn, hpondn are those arrays uploads neither: one device-to-device
+ * copy each from the pond stage's buffer.  The record ends with the next cice_step_ponds, with cice_thermo_batch_alloc
+ * and with mode 0; with the chain off, or with other pointers, cice_step_radiation_dedd does what it always did.  Nothing
+ * is deferred: the host arrays are valid at every moment.  The caller's part: nothing writes to the two host arrays
+ * between the two calls. */
+int cice_pond_chain(cice_ctx *ctx, int mode);
+
 /* ---- horizontal transport by incremental remapping ----------------------------------
  * cice_transport_init ≙ init_transport (source/ice_transport_driver.F90:81; advection = 'remap'): tracer
  * dependencies from ntrcr / trcr_depend (ice_init.F90:848-852: 0 area tracer, 1 ice-volume, 2 snow-volume tracer),
